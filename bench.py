@@ -17,6 +17,13 @@ whole-job samples/sec (all ranks).
 The reference's published numbers for this metric are 709.84 samples/sec
 (defaults) and 653.10 (long run) on unspecified CPU hardware
 (docs/benchmarks_tutorial.rst:20-37) -> vs_baseline = value / 709.84.
+
+A plain run sets up, warms up, times ``--steps`` steps and prints one JSON
+result line.  Warmup steps and timed steps have the same size (see
+``--min-region``), so ``ms_per_step`` holds for both.  ``--dump-outputs DIR`` also saves the last timed batch as
+.npy files (same arguments -> same dataset, same seeded order, same batch),
+so two builds can be compared output for output.  ``--full`` adds the
+diagnostics the headline figure does not need.
 """
 import argparse
 import json
@@ -150,6 +157,7 @@ def bench_imagenet(args, rank, world, device, dist):
 
     def step():
         b = next(it)
+        _remember(args, b)
         return b['image'].shape[0]
 
     result = _run_timed(args, step, device, dist, world)
@@ -164,7 +172,7 @@ def bench_imagenet(args, rank, world, device, dist):
     if rank == 0 and reader.diagnostics.get('cpu_assist_columns'):
         print('WARNING: cpu-assist columns: {}'.format(
             reader.diagnostics['cpu_assist_columns']), file=sys.stderr)
-    if os.environ.get('PSA_TIMING') == '1' and rank == 0:
+    if _timing_wanted(args) and rank == 0:
         diag = reader.diagnostics
         print('stage_times:', diag.get('stage_times'),
               'staging_allocs:', diag.get('staging_allocs'),
@@ -213,12 +221,13 @@ def bench_scalar(args, rank, world, device, dist):
 
     def step():
         b = next(it)
+        _remember(args, b)
         return b['id'].shape[0]
 
     result = _run_timed(args, step, device, dist, world)
     reader.stop()
     reader.join()
-    if os.environ.get('PSA_TIMING') == '1' and rank == 0:
+    if _timing_wanted(args) and rank == 0:
         print('stage_times:', reader.diagnostics.get('stage_times'),
               file=sys.stderr)
     return result, {
@@ -241,16 +250,22 @@ def bench_helloworld_cpu(args, rank, world, device, dist):
     url = _dataset_dir('hello_{}'.format(n_rows), rank, dist,
                        lambda u: create_hello_world_dataset(
                            u, num_rows=n_rows, rowgroup_size_mb=4))
+    # the reference config shuffles unseeded; a dump needs the same rows in
+    # the same order from run to run, which the seeded readout guarantees
     reader = make_reader(url, reader_pool_type='thread', workers_count=3,
-                         num_epochs=None, shuffle_row_groups=True)
+                         num_epochs=None, shuffle_row_groups=True,
+                         seed=11 if _dump_dir(args) is not None else None)
     it = iter(reader)
 
     def step():
         # the reference benchmark counts single next(reader) rows
         # (petastorm/benchmark/throughput.py:68-90); a "step" here is
         # batch_size of them so step timing stays comparable
+        row = None
         for _ in range(args.batch_size):
-            next(it)
+            row = next(it)
+        if row is not None:
+            _remember(args, row)
         return args.batch_size
 
     result = _run_timed(args, step, device, dist, world)
@@ -302,20 +317,21 @@ def bench_ngram(args, rank, world, device, dist):
 
     def step():
         b = next(it)
+        _remember(args, b)
         return b['tokens'].shape[0]
 
     # this config MEASURES the HBM-cache tier (BASELINE config 5: epoch
-    # re-reads served from HBM): warmup must cover the cold first epoch so
-    # the timed steps hit the cache steady state.  The raised warmup is
-    # reported in the JSON line.
+    # re-reads served from HBM): the untimed priming batches must cover the
+    # cold first epoch so the warmup and timed steps hit the cache steady
+    # state.
     per_rank_rows = n_rows // max(1, world)
     batch_rows = args.batch_size * 16
-    args.warmup = max(args.warmup,
-                      (per_rank_rows + batch_rows - 1) // batch_rows + 8)
+    args.prime_batches = max(
+        args.warmup, (per_rank_rows + batch_rows - 1) // batch_rows + 8)
     result = _run_timed(args, step, device, dist, world)
     reader.stop()
     reader.join()
-    if os.environ.get('PSA_TIMING') == '1' and rank == 0:
+    if _timing_wanted(args) and rank == 0:
         print('stage_times:', reader.diagnostics.get('stage_times'),
               file=sys.stderr)
     return result, {
@@ -328,11 +344,79 @@ def bench_ngram(args, rank, world, device, dist):
     }
 
 
+DUMP_BUDGET_BYTES = 60 << 20  # whole dump stays under 64 MB
+DUMP_SAMPLE_SEED = 20240
+
+
+def _remember(args, batch):
+    """Keep the newest batch of the timed path, but only when it is going
+    to be dumped: holding it otherwise delays the release of its HBM."""
+    if _dump_dir(args) is not None:
+        args.last_batch = batch
+
+
+# The bench_* functions are also driven with a hand-built namespace
+# (tools/stability_probe.py), which may lack the newer options.
+def _dump_dir(args):
+    return getattr(args, 'dump_outputs', None)
+
+
+def _timing_wanted(args):
+    return getattr(args, 'full', False) or \
+        os.environ.get('PSA_TIMING') == '1'
+
+
+def _dump_outputs(args):
+    """--dump-outputs DIR: write every numeric field of the last timed
+    batch as DIR/<field>.npy (float32; float64 for float64 and integer
+    fields).  A field larger than its share of the byte budget is cut down
+    to a fixed, seeded, sorted selection of its rows (or of its flattened
+    elements when one row alone is too large)."""
+    batch = getattr(args, 'last_batch', None)
+    if batch is None:
+        raise RuntimeError('--dump-outputs: the timed path produced no batch')
+    if hasattr(batch, '_asdict'):  # make_reader rows are namedtuples
+        batch = batch._asdict()
+    arrays = {}
+    for name, v in batch.items():
+        if isinstance(v, torch.Tensor):
+            v = v.detach().cpu().numpy()
+        else:
+            v = np.asarray(v)
+        if v.dtype.kind not in 'biuf':
+            continue  # strings, decimals, objects: nothing numeric to compare
+        wide = v.dtype.kind in 'iu' or v.dtype == np.float64
+        arrays[name] = v.astype(np.float64 if wide else np.float32)
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays))
+    rng = np.random.RandomState(DUMP_SAMPLE_SEED)
+    for name in sorted(arrays):
+        a = arrays[name]
+        if a.nbytes > share:
+            row_bytes = a.nbytes // max(1, a.shape[0]) if a.ndim else a.nbytes
+            if a.ndim and row_bytes <= share:
+                keep = np.sort(rng.choice(a.shape[0], share // row_bytes,
+                                          replace=False))
+                a = a[keep]
+            else:
+                keep = np.sort(rng.choice(a.size, share // a.itemsize,
+                                          replace=False))
+                a = a.reshape(-1)[keep]
+        np.save(os.path.join(args.dump_outputs, name + '.npy'),
+                np.ascontiguousarray(a))
+
+
 def _run_timed(args, step_fn, device, dist, world):
-    # warmup
-    warm_samples = 0
-    for _ in range(args.warmup):
-        warm_samples += step_fn()
+    # Prime the pipeline with single batches before the calibration probe,
+    # so the probe sees a warm path.  Without calibration the warmup steps
+    # below are single batches themselves and no priming is needed, unless
+    # the config asks for it in args.prime_batches (ngram: the cold first
+    # epoch).
+    prime_batches = getattr(args, 'prime_batches', None)
+    if prime_batches is None:
+        prime_batches = args.warmup if args.min_region > 0 else 0
+    for _ in range(prime_batches):
+        step_fn()
     _sync(device)
     # Calibrate how many loader batches form one timed step so the timed
     # region spans >= --min-region seconds regardless of the requested step
@@ -362,6 +446,12 @@ def _run_timed(args, step_fn, device, dist, world):
                 t = t.to(device)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             batches_per_step = int(t.item())
+    # warmup: --warmup steps of the same size as the timed ones, so that
+    # (steps + warmup) * ms_per_step is what the stepping really took
+    for _ in range(args.warmup):
+        for _ in range(batches_per_step):
+            step_fn()
+    _sync(device)
     # The calibration probe can overestimate per-batch cost under transient
     # contention, which would undershoot the region; if that happens, scale
     # batches_per_step up and re-time (every rank sees the same MAX-reduced
@@ -395,10 +485,15 @@ def _run_timed(args, step_fn, device, dist, world):
                 or attempts >= 3:
             break
         scale = max(2.0, 1.5 * args.min_region / max(elapsed, 1e-9))
-        batches_per_step = int(np.ceil(batches_per_step * scale))
+        grown = int(np.ceil(batches_per_step * scale))
+        # top the warmup steps up to the new step size
+        for _ in range(args.warmup * (grown - batches_per_step)):
+            step_fn()
+        batches_per_step = grown
     return {'elapsed_s': elapsed, 'samples': samples,
             'ms_per_step': elapsed * 1000.0 / args.steps,
-            'batches_per_step': batches_per_step}
+            'batches_per_step': batches_per_step,
+            'prime_batches': prime_batches}
 
 
 CONFIGS = {
@@ -422,7 +517,21 @@ def main():
                     help='minimum timed-region seconds: each of the K steps '
                          'consumes as many loader batches as needed to span '
                          'this (0 disables; one step == one batch then)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the batch the last '
+                         'timed step returned as DIR/<field>.npy (a seeded '
+                         'selection of rows when it exceeds the size budget). '
+                         'Implies --min-region 0: a time-calibrated step '
+                         'consumes a run-dependent number of batches, so the '
+                         'last batch would differ from run to run')
+    ap.add_argument('--full', action='store_true',
+                    help='also report what the headline figure does not '
+                         'need: the per-stage pipeline times and staging '
+                         'counters (stderr). A plain run only sets up, warms '
+                         'up, times the steps and prints the result line')
     args = ap.parse_args()
+    if args.dump_outputs is not None:
+        args.min_region = 0.0
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(_self_spawn(args))
@@ -449,10 +558,17 @@ def main():
     result, config = CONFIGS[args.config](args, rank, world, device, dist)
 
     if rank == 0:
+        if args.dump_outputs is not None:
+            _dump_outputs(args)
         value = result['samples'] / result['elapsed_s']
         config = dict(config)
         bps = result.get('batches_per_step', 1)
         config['batches_per_step'] = bps
+        # untimed single batches consumed before calibration and warmup
+        config['prime_batches'] = result.get('prime_batches', 0)
+        # 0 marks a run whose step is one loader batch (--dump-outputs):
+        # its region is short, so value and ms_per_step are rough
+        config['min_region_s'] = args.min_region
         config['global_batch'] = config.get('global_batch', 0) * bps
         out = {
             'metric': 'samples/sec/node (make_batch_reader->PyTorch '

@@ -1,6 +1,7 @@
 """Benchmark harness, ReaderMock and CLI tools (parity: reference
 tests/test_benchmark.py + tool smoke coverage)."""
 import numpy as np
+import pytest
 
 from petastorm_amd.benchmark.dummy_reader import DummyReader
 from petastorm_amd.benchmark.throughput import reader_throughput
@@ -134,6 +135,169 @@ def test_bench_py_contract(tmp_path):
     # calibration, then run the timed region faster
     assert j['timed_region_s'] >= 0.2
     assert j['config']['batches_per_step'] >= 1
+
+
+def _run_bench(tmp_path, argv):
+    """Run bench.py in a fresh process; returns its JSON result line."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import time
+    env = dict(os.environ, PSA_BENCH_DATA=str(tmp_path / 'data'))
+    t0 = time.perf_counter()
+    out = subprocess.run(
+        [sys.executable, 'bench.py'] + argv,
+        capture_output=True, text=True, timeout=300,
+        cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+        env=env)
+    wall = time.perf_counter() - t0
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1, out.stdout[-2000:]
+    j = json.loads(lines[0])
+    # warmup and timed steps are the same size: all of them together fit
+    # in the run
+    assert 0 < (j['steps'] + j['warmup']) * j['ms_per_step'] / 1e3 <= wall
+    return j, out.stderr
+
+
+def _load_dump(d):
+    import os
+    return {f: np.load(os.path.join(str(d), f)) for f in sorted(os.listdir(str(d)))}
+
+
+def _assert_dumps_equal(tmp_path, argv, extra_a=()):
+    """Two fresh runs with the same arguments dump the same arrays
+    (``extra_a``: options for the first run that must not change them).
+    Returns the first run's result line, the arrays and both stderrs."""
+    j1, err1 = _run_bench(tmp_path, argv + list(extra_a) +
+                          ['--dump-outputs', str(tmp_path / 'a')])
+    j2, err2 = _run_bench(tmp_path,
+                          argv + ['--dump-outputs', str(tmp_path / 'b')])
+    a, b = _load_dump(tmp_path / 'a'), _load_dump(tmp_path / 'b')
+    assert a and sorted(a) == sorted(b)
+    assert sum(v.nbytes for v in a.values()) <= 64 * 1000 * 1000
+    for name in a:
+        assert name.endswith('.npy')
+        assert a[name].dtype in (np.float32, np.float64), name
+        assert a[name].size > 0, name
+        np.testing.assert_array_equal(a[name], b[name], err_msg=name)
+    for j in (j1, j2):
+        # a dump run takes one loader batch per step, whatever --min-region,
+        # and its result line says so
+        assert j['config']['batches_per_step'] == 1
+        assert j['config']['min_region_s'] == 0
+        assert j['ms_per_step'] > 0
+    return j1, a, err1, err2
+
+
+def test_bench_py_dump_outputs_and_full(tmp_path):
+    """--dump-outputs writes the last timed batch as float .npy files,
+    identically from run to run; --full is accepted and leaves the result
+    line's keys and fixed fields as they are (this config has no stage
+    diagnostics to add; the GPU test below checks those)."""
+    argv = ['--config', 'helloworld', '--rows', '40', '--steps', '2',
+            '--warmup', '1', '--batch-size', '5']
+    j, dump, _, _ = _assert_dumps_equal(tmp_path, argv)
+    assert j['steps'] == 2 and j['warmup'] == 1
+    assert {'id.npy', 'image1.npy', 'array_4d.npy'} <= set(dump)
+    assert dump['image1.npy'].shape == (128, 256, 3)
+
+    plain, _ = _run_bench(tmp_path, argv + ['--min-region', '0.2'])
+    full, _ = _run_bench(tmp_path, argv + ['--min-region', '0.2', '--full'])
+    assert sorted(plain) == sorted(full)
+    for key in ('metric', 'unit', 'higher_is_better', 'dtype', 'steps'):
+        assert plain[key] == full[key], key
+    # a calibrated run is told apart from a dump run by its result line
+    assert plain['config']['min_region_s'] == 0.2
+    assert plain['config']['prime_batches'] == 1
+
+
+def test_bench_py_warmup_steps_match_timed_steps(tmp_path):
+    """With a calibrated region (several loader batches per step) and more
+    warmup than timed steps, (steps + warmup) * ms_per_step still fits in
+    the run's wall time (checked in _run_bench)."""
+    j, _ = _run_bench(tmp_path, ['--config', 'helloworld', '--rows', '40',
+                                 '--steps', '2', '--warmup', '4',
+                                 '--batch-size', '5', '--min-region', '0.5'])
+    assert j['steps'] == 2 and j['warmup'] == 4
+    assert j['config']['batches_per_step'] > 1
+
+
+def _stability_probe():
+    import importlib.util
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location(
+        'stability_probe', os.path.join(root, 'tools', 'stability_probe.py'))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_stability_probe_namespace_drives_bench(tmp_path, monkeypatch):
+    """tools/stability_probe.py drives the bench_* functions with its own
+    hand-built namespace and its own timing loop (old five-argument
+    signature): step() and the code after the loop must work with both."""
+    import torch
+    import bench
+    probe = _stability_probe()
+    monkeypatch.setenv('PSA_BENCH_DATA', str(tmp_path))
+    args = probe.bench_args('helloworld')
+    assert not hasattr(args, 'dump_outputs') and not hasattr(args, 'full')
+    args.rows, args.batch_size = 40, 5
+    got = []
+
+    def fake_run_timed(a, step_fn, dev, dist, world):
+        got.extend([step_fn(), step_fn()])
+        return {'elapsed_s': 1.0, 'samples': sum(got), 'ms_per_step': 500.0}
+
+    monkeypatch.setattr(bench, '_run_timed', fake_run_timed)
+    result, _ = bench.bench_helloworld_cpu(args, 0, 1, torch.device('cpu'),
+                                           None)
+    assert got == [5, 5] and result['samples'] == 10
+    assert bench._timing_wanted(args) is False
+
+
+@pytest.mark.gpu
+def test_stability_probe_runs_flagship_config(tmp_path, monkeypatch):
+    """The probe's own run_config() on the imagenet pipeline (small store,
+    half a second): every step and the teardown run with its namespace."""
+    import sys
+    probe = _stability_probe()
+    monkeypatch.setenv('PSA_BENCH_DATA', str(tmp_path))
+    monkeypatch.setenv('PSA_IMAGENET_RPG', '32')   # 24 x 32 = 768 rows
+    monkeypatch.delenv('PSA_SCALAR_COMPRESSION', raising=False)
+    monkeypatch.delenv('PSA_TIMING', raising=False)
+    monkeypatch.setattr(sys, 'argv', list(sys.argv))
+    monkeypatch.setattr(sys, 'path', list(sys.path))
+    windows = probe.run_config('imagenet', 0.5)
+    assert windows == []   # a window is 5 s long; none closes in 0.5 s
+
+
+@pytest.mark.gpu
+def test_bench_py_dump_outputs_gpu(tmp_path, monkeypatch):
+    """Flagship config: the dumped last batch (normalized NCHW fp32 images +
+    labels) is identical across two fresh runs, with or without --full;
+    --full adds the stage diagnostics on stderr, a run without it has
+    none."""
+    monkeypatch.setenv('PSA_IMAGENET_RPG', '64')
+    monkeypatch.delenv('PSA_TIMING', raising=False)
+    argv = ['--gpus', '1', '--rows', '256', '--batch-size', '32',
+            '--steps', '3', '--warmup', '2']
+    j, dump, err_full, err_plain = _assert_dumps_equal(
+        tmp_path, argv, extra_a=['--full'])
+    assert 'stage_times:' in err_full and 'staging_allocs:' in err_full
+    assert 'stage_times:' not in err_plain
+    assert j['dtype'] == 'fp32' and j['steps'] == 3
+    assert dump['image.npy'].shape == (32, 3, 224, 224)
+    assert dump['image.npy'].dtype == np.float32
+    assert dump['label.npy'].shape == (32,)
+    # labels are row index % 1000 of a 256-row store
+    lab = dump['label.npy']
+    assert np.all(lab == np.round(lab)) and lab.min() >= 0 and lab.max() < 256
+    assert np.isfinite(dump['image.npy']).all()
 
 
 def test_reencode_dataset_adds_restart_markers(tmp_path):

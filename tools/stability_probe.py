@@ -24,14 +24,19 @@ def _hbm_mb():
     return torch.cuda.memory_allocated() / (1 << 20)
 
 
+def bench_args(name):
+    """The namespace the bench_* functions are driven with (bench.py reads
+    its newer options with defaults, so they need not be listed here)."""
+    return argparse.Namespace(gpus=1, steps=10, warmup=2, batch_size=256,
+                              config=name, rows=None)
+
+
 def run_config(name, seconds):
     sys.argv = ['bench.py']
     sys.path.insert(0, os.path.dirname(os.path.dirname(
         os.path.abspath(__file__))))
     import bench
-    import argparse as ap
-    args = ap.Namespace(gpus=1, steps=10, warmup=2, batch_size=256,
-                        config=name, rows=None)
+    args = bench_args(name)
     device = torch.device('cuda')
 
     # build the loader exactly as bench.py does, then loop it ourselves
