@@ -4,11 +4,14 @@ Replaces the Arrow C++ decode inside ``piece.read`` of the reference
 (petastorm/arrow_reader_worker.py:358) with HIP kernels:
 
 * page headers: native thrift-compact walk (ops csrc/thrift_pages.cpp, host)
-* snappy pages: ``snappy_decompress_batch`` (wave-per-page)
-* PLAIN fixed-width values: ``varlen_gather`` (funnel-shift copy) straight
-  into the column tensor
+* snappy / LZ4 / gzip pages: ``snappy_decompress_batch`` (wave-per-page),
+  ``lz4_decompress_batch``, ``inflate_batch``; ZSTD pages on host threads
+* PLAIN fixed-width values: ``plain_fixed_decode_batch`` — definition
+  levels and values in one fused launch, straight into the column tensor
 * RLE/bit-packed definition levels & dictionary indices:
   ``rle_hybrid_decode_batch``
+* DELTA_BINARY_PACKED, DELTA_(LENGTH_)BYTE_ARRAY, BYTE_STREAM_SPLIT and
+  boolean pages: a batch kernel each
 * PLAIN byte-array values: per-value (offset, length) tables; blob bytes are
   decoded *in place* by the codec kernels (jpeg/npy) — never copied per value
 * NdarrayCodec: ``npy_payload_offsets`` + ``varlen_gather`` into a dense
@@ -17,7 +20,9 @@ Replaces the Arrow C++ decode inside ``piece.read`` of the reference
 
 * CompressedImageCodec(png) / CompressedNdarrayCodec: DEFLATE inflate +
   unfilter kernels (ops csrc/inflate.hip)
-* DataPageV2, GZIP pages and dictionary-encoded columns are native too
+* V1 and V2 data pages share one pipeline (``_decode_chunk``): a locator
+  per page version, then common decompression, levels and value dispatch;
+  dictionary-encoded columns are native under V1
 
 Columns outside the GPU fast path (strings for Python consumption,
 exotic encodings/types) decode on the CPU codec path and upload — the
@@ -25,7 +30,7 @@ decoder reports which columns took the assist so benchmarks and tests can
 assert the hot path stays native.
 """
 
-import os
+import collections
 
 import numpy as np
 import torch
@@ -54,6 +59,50 @@ _PHYS_TO_TORCH = {
 }
 
 _SLACK = 16  # kernels may read a few bytes past the end of a stream
+
+# codecs decompressed by device kernels (ZSTD pages decompress on the host,
+# in prepare_host, and the chunk then decodes as UNCOMPRESSED)
+_DEVICE_CODECS = ('SNAPPY', 'GZIP', 'LZ4')
+
+# What a DataPageV2 chunk may use of the value dispatch in _decode_chunk:
+# no dictionary encodings, no RLE booleans, no INT96.  Such chunks, and V2
+# chunks that mix encodings or carry repetition levels, take the CPU assist.
+_V2_ENCODINGS = frozenset([_ENC_PLAIN, _ENC_DELTA_BINARY,
+                           _ENC_DELTA_LENGTH_BA, _ENC_DELTA_BA,
+                           _ENC_BYTE_STREAM_SPLIT])
+_V2_PHYSICAL = frozenset(_PHYS_TO_TORCH) | {'BYTE_ARRAY', 'BOOLEAN',
+                                            'FIXED_LEN_BYTE_ARRAY'}
+
+# Where the data pages of one column chunk live, V1 and V2 alike (filled in
+# by _locate_v1 / _locate_v2).  Page j has ``page_nval[j]`` rows, nulls
+# included, and its values at ``val_buf[val_start[j]:val_end[j]]``;
+# ``host_visible`` says the same offsets address the chunk's host buffer.
+# Its definition levels are at ``lev_buf[lev_start[j]:lev_end[j]]``,
+# ``lev_bits`` wide; a row is non-null where its level is non-zero
+# (``lev_present`` None) or equals ``lev_present``.  ``lev_buf`` is None for
+# a V1 chunk without levels (max_def == 0) or bound for the fused kernel,
+# which finds V1 levels itself at the head of each value span.
+# ``dict_span`` is (start, end, n_values) of the dictionary page in
+# ``val_buf``, or None.  ``def_mode`` is plain_fixed_decode_batch's: 0 no
+# levels, 1 V1 levels inline in the value spans, 2 V2 levels in ``lev_buf``.
+_ChunkPages = collections.namedtuple('_ChunkPages', [
+    'name', 'val_buf', 'val_start', 'val_end', 'page_nval', 'host_visible',
+    'lev_buf', 'lev_start', 'lev_end', 'lev_bits', 'lev_present',
+    'dict_span', 'def_mode'])
+
+
+def _excl_scan(counts):
+    """Exclusive prefix sum, int64: where each of ``counts`` items starts."""
+    off = np.zeros(len(counts), dtype=np.int64)
+    np.cumsum(counts[:-1], out=off[1:])
+    return off
+
+
+def _tag_valid(col, valid, all_valid):
+    """Per-ROW validity of a ByteArrayColumn, normalized to None when every
+    row is non-null."""
+    col.valid = None if all_valid else valid
+    return col
 
 
 class ByteArrayColumn(object):
@@ -320,9 +369,7 @@ class GpuRowGroupDecoder(object):
         dlb = pages['dl_bytes'].numpy().astype(np.int64)
         rlb = pages['rl_bytes'].numpy().astype(np.int64)
         v2c = pages['v2_is_compressed'].numpy().astype(bool)
-        u_off = np.zeros(len(offs), dtype=np.int64)
-        if len(offs) > 1:
-            u_off[1:] = np.cumsum(usz)[:-1]
+        u_off = _excl_scan(usz)
         hbuf = torch.empty(int(usz.sum()) + _SLACK, dtype=torch.uint8,
                            pin_memory=self._pin_memory)
         hb_src = host_buf.numpy()
@@ -403,12 +450,10 @@ class GpuRowGroupDecoder(object):
     def decode(self, host_buf, chunk_meta, schema, host_plan=None):
         """Decode the requested columns.  Returns dict name ->
         torch tensor (fixed columns) or ByteArrayColumn (binary)."""
-        ext = self._ext
-        dev = self.device
         n_rows = chunk_meta['num_rows']
         if host_plan is None:
             host_plan = self.prepare_host(host_buf, chunk_meta, schema)
-        dbuf = host_buf.to(dev, non_blocking=True)
+        dbuf = host_buf.to(self.device, non_blocking=True)
 
         out = {}
         for ch in chunk_meta['chunks']:
@@ -424,9 +469,8 @@ class GpuRowGroupDecoder(object):
                 # reassembly too)
                 out[name] = self._cpu_assist_marker(name)
                 continue
-            col = self._decode_chunk(ext, dev, dbuf, host_buf, ch,
-                                     host_plan[name], n_rows, schema)
-            out[name] = col
+            out[name] = self._decode_chunk(dbuf, host_buf, ch,
+                                           host_plan[name], n_rows, schema)
         return out, dbuf
 
     def _cpu_assist_marker(self, name):
@@ -434,432 +478,239 @@ class GpuRowGroupDecoder(object):
         return None
 
     # ------------------------------------------------------------------
-    def _decode_chunk(self, ext, dev, dbuf, host_buf, ch, plan_entry, n_rows,
-                      schema):
+    def _decode_chunk(self, dbuf, host_buf, ch, plan_entry, n_rows, schema):
+        """One column chunk -> tensor, ByteArrayColumn, or None (CPU
+        assist).  A locator per page version describes the pages
+        (_ChunkPages); from there V1 and V2 share the fused PLAIN kernel,
+        the level decoder and the value dispatch."""
         pages = plan_entry['pages']
         if ch['compression'] == 'ZSTD':
             z = plan_entry.get('zstd')
             if z is None:  # defensive: plan missing (never in normal flow)
                 return self._cpu_assist_marker(ch['name'])
             host_buf = z['host_buf']
-            dbuf = host_buf.to(dev, non_blocking=True)
+            dbuf = host_buf.to(self.device, non_blocking=True)
             pages = z['pages']
             ch = dict(ch, compression='UNCOMPRESSED')
-        self._plan_entry = plan_entry
+        name, phys, max_def = ch['name'], ch['physical'], ch['max_def']
         page_type = pages['page_type'].numpy()
-        data_off = pages['data_off'].numpy()       # relative to chunk walk
-        comp_size = pages['comp_size'].numpy()
-        uncomp_size = pages['uncomp_size'].numpy()
-        num_values = pages['num_values'].numpy()
-        encoding = pages['encoding'].numpy()
-        n_pages = len(page_type)
-        snappy = ch['compression'] in ('SNAPPY', 'GZIP', 'LZ4')
-
-        # V2 pages compress ONLY the values section, so they must never go
-        # through the whole-page decompression below — dispatch first
-        data_idx_early = [i for i in range(n_pages)
-                          if page_type[i] in (_PAGE_DATA_V1, _PAGE_DATA_V2)]
-        if not data_idx_early:
-            return torch.empty(0, device=dev)
-        if any(page_type[i] == _PAGE_DATA_V2 for i in data_idx_early):
-            return self._decode_v2_chunk(ext, dev, dbuf, host_buf, ch,
-                                         schema,
-                                         pages, data_idx_early, n_rows)
-
-        # 1) page payload location: either in dbuf directly, or in a
-        #    decompressed scratch buffer
-        if snappy:
-            total_un = int(uncomp_size.sum())
-            ubuf = torch.empty(total_un + _SLACK, dtype=torch.uint8,
-                               device=dev)
-            u_off = np.zeros(n_pages + 1, dtype=np.int64)
-            u_off[1:] = np.cumsum(uncomp_size)
-            status = self._status(n_pages)
-            if ch['compression'] == 'SNAPPY':
-                ext.snappy_decompress_batch(
-                    dbuf, self._up(data_off.astype(np.int64)),
-                    self._up((data_off + comp_size).astype(np.int64)),
-                    ubuf, self._up(u_off[:-1]),
-                    self._up(uncomp_size.astype(np.int64)), status)
-                self._check(status, 'snappy:' + ch['name'])
-            elif ch['compression'] == 'LZ4':
-                blocks = plan_entry.get('lz4_blocks')
-                if blocks is None:
-                    blocks = self._lz4_parse_framing(host_buf, pages)
-                blk_src = blocks['src']
-                blk_dst = u_off[blocks['page']] + blocks['dst_rel']
-                bstatus = self._status(len(blk_src))
-                ext.lz4_decompress_batch(
-                    dbuf, self._up(blk_src),
-                    self._up(blk_src + blocks['src_len']),
-                    ubuf, self._up(blk_dst),
-                    self._up(blocks['dst_len']), bstatus)
-                self._check(bstatus, 'lz4:' + ch['name'])
-            else:  # GZIP: each page is one gzip member -> inflate kernel
-                produced = torch.zeros(n_pages, dtype=torch.int64,
-                                       device=dev)
-                ext.inflate_batch(
-                    dbuf, self._up(data_off.astype(np.int64)),
-                    self._up(comp_size.astype(np.int64)),
-                    torch.arange(n_pages, dtype=torch.int32, device=dev),
-                    torch.ones(n_pages, dtype=torch.int32, device=dev),
-                    ubuf, self._up(u_off[:-1]),
-                    self._up(uncomp_size.astype(np.int64)), produced, 2,
-                    status)
-                self._check(status, 'gzip:' + ch['name'])
-            page_buf = ubuf
-            page_start = u_off[:-1]
-            host_visible = False
+        data_idx = np.flatnonzero((page_type == _PAGE_DATA_V1) |
+                                  (page_type == _PAGE_DATA_V2))
+        if not len(data_idx):
+            return torch.empty(0, device=self.device)
+        enc = pages['encoding'].numpy()[data_idx]
+        data_enc = enc[0]
+        # PLAIN fixed-width columns decode def levels + values in ONE fused
+        # kernel with zero host syncs (common case: pyarrow marks every
+        # column OPTIONAL, so max_def==1 even for null-free data)
+        fused = data_enc == _ENC_PLAIN and \
+            (phys in _PHYS_TO_TORCH or phys == 'INT96')
+        if (page_type[data_idx] == _PAGE_DATA_V2).any():
+            if phys not in _V2_PHYSICAL or data_enc not in _V2_ENCODINGS \
+                    or (enc != data_enc).any() \
+                    or pages['rl_bytes'].numpy()[data_idx].any():
+                return self._cpu_assist_marker(name)
+            pg = self._locate_v2(dbuf, host_buf, ch, pages, data_idx)
         else:
-            page_buf = dbuf
-            page_start = data_off.astype(np.int64)
-            host_visible = True
+            pg = self._locate_v1(dbuf, host_buf, ch, pages, data_idx,
+                                 plan_entry.get('lz4_blocks'),
+                                 split_levels=not fused)
+        if fused and phys == 'INT96':
+            return self._int96_timestamps(pg)
+        if fused:
+            dtype, esize = _PHYS_TO_TORCH[phys]
+            out, _ = self._plain_fixed(
+                pg, esize, self._fill_for(schema, name, phys))
+            return out.view(dtype)
 
-        # 2) split dict page / data pages
-        dict_idx = [i for i in range(n_pages) if page_type[i] == _PAGE_DICT]
-        data_idx = [i for i in range(n_pages)
-                    if page_type[i] in (_PAGE_DATA_V1, _PAGE_DATA_V2)]
-        if not data_idx:
-            return torch.empty(0, device=dev)
-        data_enc = encoding[data_idx[0]]
-
-        max_def = ch['max_def']
-        phys = ch['physical']
-
-        # fast path: PLAIN fixed-width columns decode def levels + values in
-        # ONE fused kernel with zero host syncs (common case: pyarrow marks
-        # every column OPTIONAL, so max_def==1 even for null-free data)
-        if data_enc == _ENC_PLAIN and phys in _PHYS_TO_TORCH:
-            sizes = uncomp_size if snappy else comp_size
-            page_nval = num_values[data_idx]
-            p_start = np.array([page_start[i] for i in data_idx],
-                               dtype=np.int64)
-            p_end = np.array([page_start[i] + sizes[i] for i in data_idx],
-                             dtype=np.int64)
-            row0 = np.zeros(len(data_idx), dtype=np.int64)
-            row0[1:] = np.cumsum(page_nval)[:-1]
-            fill = self._fill_for(schema, ch['name'], phys)
-            return self._plain_fixed_fused(ext, dev, page_buf, p_start,
-                                           p_end, page_nval, row0, max_def,
-                                           n_rows, phys, ch['name'],
-                                           fill=fill)
-        if data_enc == _ENC_PLAIN and phys == 'INT96':
-            sizes = uncomp_size if snappy else comp_size
-            page_nval = num_values[data_idx]
-            p_start = np.array([page_start[i] for i in data_idx],
-                               dtype=np.int64)
-            p_end = np.array([page_start[i] + sizes[i] for i in data_idx],
-                             dtype=np.int64)
-            row0 = np.zeros(len(data_idx), dtype=np.int64)
-            row0[1:] = np.cumsum(page_nval)[:-1]
-            return self._int96_timestamps(ext, dev, page_buf, p_start,
-                                          p_end, page_nval, row0, max_def,
-                                          ch['name'])
-
-        # 3) locate per-page def-level and value sections
-        val_start = np.empty(len(data_idx), dtype=np.int64)
-        val_end = np.empty(len(data_idx), dtype=np.int64)
-        def_start = np.empty(len(data_idx), dtype=np.int64)
-        def_end = np.empty(len(data_idx), dtype=np.int64)
-        page_nval = num_values[data_idx]
+        # definition levels -> validity; `counts` = values actually stored
+        valid = nonnull = None
         if max_def > 0:
-            if not host_visible:
-                # def-level section length prefix lives in the decompressed
-                # buffer; fetch the 4-byte prefixes (one small D2H)
-                prefs = torch.stack([
-                    page_buf[page_start[i]:page_start[i] + 4]
-                    for i in data_idx]).cpu().numpy()
-                dl_len = (prefs[:, 0].astype(np.int64)
-                          | (prefs[:, 1].astype(np.int64) << 8)
-                          | (prefs[:, 2].astype(np.int64) << 16)
-                          | (prefs[:, 3].astype(np.int64) << 24))
-            else:
-                hb = host_buf.numpy()
-                dl_len = np.empty(len(data_idx), dtype=np.int64)
-                for j, i in enumerate(data_idx):
-                    p = page_start[i]
-                    dl_len[j] = int.from_bytes(
-                        hb[p:p + 4].tobytes(), 'little')
-            for j, i in enumerate(data_idx):
-                def_start[j] = page_start[i] + 4
-                def_end[j] = def_start[j] + dl_len[j]
-                val_start[j] = def_end[j]
-                val_end[j] = page_start[i] + uncomp_size[i] if snappy \
-                    else page_start[i] + comp_size[i]
-        else:
-            for j, i in enumerate(data_idx):
-                val_start[j] = page_start[i]
-                val_end[j] = page_start[i] + (uncomp_size[i] if snappy
-                                              else comp_size[i])
+            valid, nonnull = self._decode_levels(pg)
+        counts = pg.page_nval if nonnull is None else nonnull
+        all_valid = nonnull is None or bool((nonnull == pg.page_nval).all())
 
-        # 4) definition levels -> validity
-        valid = None
-        nonnull_per_page = None
-        if max_def > 0:
-            lv_off = np.zeros(len(data_idx) + 1, dtype=np.int64)
-            lv_off[1:] = np.cumsum(page_nval)
-            levels = torch.empty(int(lv_off[-1]), dtype=torch.int32,
-                                 device=dev)
-            status = self._status(len(data_idx))
-            ext.rle_hybrid_decode_batch(
-                page_buf, self._up(def_start), self._up(def_end),
-                torch.ones(len(data_idx), dtype=torch.int32, device=dev),
-                self._up(page_nval.astype(np.int32)),
-                self._up(lv_off[:-1]), levels, status)
-            self._check(status, 'deflevels:' + ch['name'])
-            valid = levels.bool()
-            # per-page non-null counts (needed to place value sections)
-            vmat = valid.split([int(x) for x in page_nval])
-            nonnull_per_page = np.array([int(v.sum().item()) for v in vmat],
-                                        dtype=np.int64)
-
-        # 5) values by encoding
+        # values by (encoding, physical type); _V2_ENCODINGS/_V2_PHYSICAL
+        # above say which of these a DataPageV2 chunk may reach
+        dict_enc = data_enc in (_ENC_PLAIN_DICT, _ENC_RLE_DICT) and \
+            pg.dict_span is not None
         if data_enc == _ENC_PLAIN and phys == 'BYTE_ARRAY':
-            return self._plain_byte_array(
-                ext, dev, page_buf, host_buf, val_start, val_end, page_nval,
-                nonnull_per_page, valid, host_visible, ch)
-        if data_enc in (_ENC_PLAIN_DICT, _ENC_RLE_DICT) and \
-                phys in _PHYS_TO_TORCH and dict_idx:
-            return self._dict_fixed(ext, dev, page_buf, page_start, dict_idx,
-                                    num_values, uncomp_size if snappy
-                                    else comp_size, val_start, val_end,
-                                    page_nval, nonnull_per_page, valid,
-                                    n_rows, phys)
-        if data_enc in (_ENC_PLAIN_DICT, _ENC_RLE_DICT) and \
-                phys == 'BYTE_ARRAY' and dict_idx:
-            return self._dict_byte_array(ext, dev, page_buf, page_start,
-                                         dict_idx, num_values,
-                                         uncomp_size if snappy else comp_size,
-                                         val_start, val_end, page_nval,
-                                         nonnull_per_page, valid, ch)
-        all_valid = nonnull_per_page is None or \
-            bool((nonnull_per_page == page_nval).all())
+            return self._plain_byte_array(pg, counts, valid, all_valid,
+                                          host_buf, plan_entry)
+        if dict_enc and phys in _PHYS_TO_TORCH:
+            return self._dict_fixed(pg, counts, valid, n_rows, phys)
+        if dict_enc and phys == 'BYTE_ARRAY':
+            return self._dict_byte_array(pg, counts, valid, all_valid)
         if data_enc == _ENC_DELTA_BINARY and phys in ('INT32', 'INT64') \
                 and all_valid:
-            return self._delta_fixed(ext, dev, page_buf, val_start, val_end,
-                                     page_nval, phys, ch)
+            return self._delta_fixed(pg, phys)
         if data_enc == _ENC_DELTA_LENGTH_BA and phys == 'BYTE_ARRAY':
-            return self._delta_length_byte_array(
-                ext, dev, page_buf, val_start, val_end, page_nval,
-                nonnull_per_page, valid, ch)
+            return self._delta_length_byte_array(pg, counts, valid,
+                                                 all_valid)
         if data_enc == _ENC_DELTA_BA and phys == 'BYTE_ARRAY':
-            return self._delta_byte_array(
-                ext, dev, page_buf, val_start, val_end, page_nval,
-                nonnull_per_page, valid, ch)
+            return self._delta_byte_array(pg, counts, valid, all_valid)
         if data_enc == _ENC_BYTE_STREAM_SPLIT and phys in _PHYS_TO_TORCH \
                 and all_valid:
-            return self._byte_stream_split(ext, dev, page_buf, val_start,
-                                           page_nval, phys)
+            return self._byte_stream_split(pg, phys)
         if data_enc == _ENC_PLAIN and phys == 'BOOLEAN' and all_valid:
-            return self._bool_plain(ext, dev, page_buf, val_start,
-                                    page_nval)
+            return self._bool_plain(pg)
         if data_enc == _ENC_RLE and phys == 'BOOLEAN' and all_valid:
-            # RLE-encoded booleans: u32 length prefix + hybrid runs (bw=1)
-            counts32 = page_nval.astype(np.int32)
-            total = int(counts32.sum())
-            out_off = np.zeros(len(counts32), dtype=np.int64)
-            out_off[1:] = np.cumsum(counts32)[:-1]
-            out32 = torch.empty(total, dtype=torch.int32, device=dev)
-            status = self._status(len(counts32))
-            ext.rle_hybrid_decode_batch(
-                page_buf, self._up(val_start + 4), self._up(val_end),
-                torch.ones(len(counts32), dtype=torch.int32, device=dev),
-                self._up(counts32), self._up(out_off), out32, status)
-            self._check(status, 'rlebool:' + ch['name'])
-            return out32.to(torch.bool)
+            return self._bool_rle(pg)
         if data_enc == _ENC_PLAIN and phys == 'FIXED_LEN_BYTE_ARRAY' and \
                 ch.get('type_length', 0) > 0:
-            return self._plain_flba(ext, dev, page_buf, host_buf,
-                                    val_start, page_nval,
-                                    nonnull_per_page, valid, host_visible,
+            return self._plain_flba(pg, counts, valid, all_valid, host_buf,
                                     schema, ch)
-        return self._cpu_assist_marker(ch['name'])
+        return self._cpu_assist_marker(name)
 
-    def _plain_flba(self, ext, dev, page_buf, host_buf, val_start,
-                    page_nval, nonnull_per_page, valid, host_visible,
-                    schema, ch):
-        """PLAIN FIXED_LEN_BYTE_ARRAY: values are contiguous with a
-        fixed stride.  float16 (logical Float16) views the gathered bytes
-        directly as a half tensor; everything else becomes a fixed-stride
-        ByteArrayColumn (bytes at the boundary)."""
-        L = int(ch['type_length'])
-        counts = (nonnull_per_page if nonnull_per_page is not None
-                  else page_nval).astype(np.int64)
-        total = int(counts.sum())
-        all_valid = nonnull_per_page is None or \
-            bool((nonnull_per_page == page_nval).all())
-        field = schema.fields.get(ch['name'])
-        if field is not None and field.numpy_dtype is np.float16 and \
-                all_valid and L == 2:
-            out = torch.empty(total * L + _SLACK, dtype=torch.uint8,
-                              device=dev)
-            dst_off = np.zeros(len(counts), dtype=np.int64)
-            dst_off[1:] = np.cumsum(counts * L)[:-1]
-            ext.varlen_gather(page_buf, self._up(val_start),
-                              self._up(counts * L), out,
-                              self._up(dst_off))
-            return out[:total * L].view(torch.float16)
-        starts = np.concatenate(
-            [vs + np.arange(c, dtype=np.int64) * L
-             for vs, c in zip(val_start, counts)]) if total else \
-            np.zeros(0, dtype=np.int64)
-        col = ByteArrayColumn(page_buf, self._up(starts),
-                              torch.full((total,), L, dtype=torch.int32,
-                                         device=dev),
-                              host_buf if host_visible else None,
-                              starts if host_visible else None, total)
+    def _locate_v1(self, dbuf, host_buf, ch, pages, data_idx, lz4_blocks,
+                   split_levels):
+        """V1 pages are compressed whole (levels included), the dictionary
+        page too: decompress every page of the chunk, then describe the
+        data pages.  With ``split_levels`` the u32 length prefix of each
+        page's level section is read to split levels from values — a small
+        D2H when the chunk was decompressed on device, so the fused PLAIN
+        path asks for the whole-page spans instead."""
+        name, max_def = ch['name'], ch['max_def']
+        data_off = pages['data_off'].numpy()
+        size = pages['comp_size'].numpy()
+        host_visible = ch['compression'] not in _DEVICE_CODECS
         if host_visible:
-            col.host_val_len = np.full(total, L, dtype=np.int64)
-        if valid is not None and not all_valid:
-            col.valid = valid
-        return col
+            buf, page_start = dbuf, data_off
+        else:
+            src_end = data_off + size
+            size = pages['uncomp_size'].numpy()
+            page_start = _excl_scan(size)
+            buf = torch.empty(int(size.sum()) + _SLACK, dtype=torch.uint8,
+                              device=self.device)
+            self._decompress(ch['compression'], dbuf, host_buf, data_off,
+                             src_end, buf, page_start, size, name,
+                             lz4_blocks)
+        start = page_start[data_idx]
+        end = start + size[data_idx]
+        lev_buf = lev_start = lev_end = None
+        if split_levels and max_def > 0:
+            if host_visible:
+                prefs = host_buf.numpy()[start[:, None] + np.arange(4)]
+            else:
+                prefs = torch.stack([buf[p:p + 4] for p in start]) \
+                    .cpu().numpy()
+            lev_len = (prefs.astype(np.int64) << np.arange(0, 32, 8)).sum(1)
+            lev_buf, lev_start = buf, start + 4
+            lev_end = lev_start + lev_len
+            start = lev_end
+        num_values = pages['num_values'].numpy()
+        dict_span = None
+        dict_idx = np.flatnonzero(pages['page_type'].numpy() == _PAGE_DICT)
+        if len(dict_idx):
+            di = dict_idx[0]
+            dict_span = (int(page_start[di]), int(page_start[di] + size[di]),
+                         int(num_values[di]))
+        # levels are read 1 bit wide: right for max_def == 1 only
+        return _ChunkPages(
+            name, val_buf=buf, val_start=start, val_end=end,
+            page_nval=num_values[data_idx], host_visible=host_visible,
+            lev_buf=lev_buf, lev_start=lev_start, lev_end=lev_end,
+            lev_bits=1, lev_present=None, dict_span=dict_span,
+            def_mode=1 if max_def > 0 else 0)
 
-    def _int96_timestamps(self, ext, dev, page_buf, p_start, p_end,
-                          page_nval, row0, max_def, name):
-        """PLAIN INT96 (legacy Spark timestamps): 8B nanos-in-day +
-        4B julian day -> int64 nanoseconds since the unix epoch; the
-        reader boundary surfaces datetime64[ns]."""
-        total = int(page_nval.sum())
-        out = torch.empty(total * 12 + _SLACK, dtype=torch.uint8,
-                          device=dev)
-        status = self._status(len(p_start))
-        empty8 = torch.empty(0, dtype=torch.uint8, device=dev)
-        empty64 = torch.empty(0, dtype=torch.int64, device=dev)
-        valid_out = torch.empty(total if max_def > 0 else 0,
-                                dtype=torch.uint8, device=dev)
-        ext.plain_fixed_decode_batch(
-            page_buf, self._up(p_start), self._up(p_end),
-            self._up(page_nval.astype(np.int32)), self._up(row0),
-            1 if max_def > 0 else 0, 12, 0,
-            empty8, empty64, empty64, out, valid_out, status)
-        self._check(status, 'int96:' + name)
-        m = out[:total * 12].view(total, 12)
-        nanos = m[:, :8].contiguous().view(torch.int64).reshape(total)
-        day = m[:, 8:12].contiguous().view(torch.int32).reshape(total) \
-            .to(torch.int64)
-        ns = (day - 2440588) * 86_400_000_000_000 + nanos
-        if max_def > 0:
-            # null rows -> int64 min == numpy NaT after the boundary's
-            # datetime64 view (CPU-route parity)
-            ns = torch.where(valid_out.bool(), ns,
-                             torch.tensor(np.iinfo(np.int64).min,
-                                          dtype=torch.int64, device=dev))
-        return ns
+    def _locate_v2(self, dbuf, host_buf, ch, pages, data_idx):
+        """DataPageV2: levels are stored uncompressed with explicit byte
+        lengths ahead of the values; only the values section is compressed
+        (Parquet format spec), and a page may individually opt out via
+        is_compressed (writers skip compression when it does not shrink
+        the page).  Compressed sections decompress into one buffer; raw
+        pages of such a chunk are copied in next to them."""
+        name, max_def = ch['name'], ch['max_def']
+        data_off = pages['data_off'].numpy()[data_idx]
+        dl = pages['dl_bytes'].numpy()[data_idx]
+        lev_start = data_off + pages['rl_bytes'].numpy()[data_idx]
+        val_buf, val_start = dbuf, lev_start + dl
+        val_end = data_off + pages['comp_size'].numpy()[data_idx]
+        compressed = pages['v2_is_compressed'].numpy()[data_idx] \
+            .astype(bool) & (ch['compression'] in _DEVICE_CODECS)
+        if compressed.any():
+            v_un = pages['uncomp_size'].numpy()[data_idx] \
+                - (val_start - data_off)
+            u_off = _excl_scan(v_un)
+            val_buf = torch.empty(int(v_un.sum()) + _SLACK,
+                                  dtype=torch.uint8, device=self.device)
+            ci = np.flatnonzero(compressed)
+            self._decompress(ch['compression'], dbuf, host_buf,
+                             val_start[ci], val_end[ci], val_buf, u_off[ci],
+                             v_un[ci], name)
+            ri = np.flatnonzero(~compressed)
+            if len(ri):
+                self._ext.varlen_gather(dbuf, self._up(val_start[ri]),
+                                        self._up(v_un[ri]), val_buf,
+                                        self._up(u_off[ri]))
+            val_start, val_end = u_off, u_off + v_un
+        # a REQUIRED column keeps its (empty) level spans: the fused kernel
+        # takes them as arguments whatever its def mode
+        return _ChunkPages(
+            name, val_buf=val_buf, val_start=val_start, val_end=val_end,
+            page_nval=pages['num_values'].numpy()[data_idx],
+            host_visible=False,
+            lev_buf=dbuf, lev_start=lev_start, lev_end=lev_start + dl,
+            lev_bits=max(1, int(np.ceil(np.log2(max_def + 1)))),
+            lev_present=max_def, dict_span=None,
+            def_mode=2 if max_def > 0 else 0)
 
-    def _bool_plain(self, ext, dev, page_buf, val_start, page_nval):
-        """PLAIN BOOLEAN: bit-packed LSB-first -> bool tensor."""
-        counts = page_nval.astype(np.int32)
-        total = int(counts.sum())
-        out_off = np.zeros(len(counts), dtype=np.int64)
-        out_off[1:] = np.cumsum(counts)[:-1]
-        out = torch.empty(total + _SLACK, dtype=torch.uint8, device=dev)
-        ext.bool_unpack_batch(page_buf, self._up(val_start),
-                              self._up(counts), self._up(out_off), out)
-        return out[:total].to(torch.bool)
+    def _decompress(self, codec, src_buf, host_buf, src_start, src_end,
+                    dst_buf, dst_off, dst_len, name, lz4_blocks=None):
+        """Decompress ``src_buf[src_start[i]:src_end[i]]`` into ``dst_len[i]``
+        bytes at ``dst_buf[dst_off[i]]`` with the codec's kernel, and queue
+        its status.  LZ4 spans are framed into raw blocks first (see
+        _lz4_spans), on ``host_buf``, unless ``lz4_blocks`` carries the
+        framing prepare_host already parsed on the IO thread."""
+        ext, dev, n = self._ext, self.device, len(src_start)
+        if codec == 'SNAPPY':
+            status = self._status(n)
+            ext.snappy_decompress_batch(
+                src_buf, self._up(src_start), self._up(src_end), dst_buf,
+                self._up(dst_off), self._up(dst_len), status)
+        elif codec == 'LZ4':
+            b = lz4_blocks
+            if b is None:
+                b = self._lz4_spans(host_buf.numpy(), src_start,
+                                    src_end - src_start, dst_len)
+            status = self._status(len(b['src']))
+            ext.lz4_decompress_batch(
+                src_buf, self._up(b['src']),
+                self._up(b['src'] + b['src_len']), dst_buf,
+                self._up(dst_off[b['page']] + b['dst_rel']),
+                self._up(b['dst_len']), status)
+        else:  # GZIP: each span is one gzip member -> inflate kernel
+            status = self._status(n)
+            produced = torch.zeros(n, dtype=torch.int64, device=dev)
+            ext.inflate_batch(
+                src_buf, self._up(src_start), self._up(src_end - src_start),
+                torch.arange(n, dtype=torch.int32, device=dev),
+                torch.ones(n, dtype=torch.int32, device=dev),
+                dst_buf, self._up(dst_off), self._up(dst_len), produced, 2,
+                status)
+        self._check(status, codec.lower() + ':' + name)
 
-    def _byte_stream_split(self, ext, dev, page_buf, val_start, page_nval,
-                           phys):
-        """BYTE_STREAM_SPLIT: de-interleave K byte planes."""
-        dtype, esize = _PHYS_TO_TORCH[phys]
-        counts = page_nval.astype(np.int32)
-        total = int(counts.sum())
-        out_off = np.zeros(len(counts), dtype=np.int64)
-        out_off[1:] = np.cumsum(counts)[:-1]
-        out = torch.empty(total * esize + _SLACK, dtype=torch.uint8,
-                          device=dev)
-        ext.byte_stream_split_batch(page_buf, self._up(val_start),
-                                    self._up(counts), self._up(out_off),
-                                    out, esize)
-        return out[:total * esize].view(dtype)
-
-    def _delta_byte_array(self, ext, dev, page_buf, val_start, val_end,
-                          page_nval, nonnull_per_page, valid, ch):
-        """DELTA_BYTE_ARRAY (front-coded strings): lengths pass -> exact
-        output sizing (ONE host sync — unavoidable: materialized size is
-        data-dependent) -> reconstruct pass.  Values land in a fresh
-        device buffer; standard ByteArrayColumn consumers follow."""
-        counts = (nonnull_per_page if nonnull_per_page is not None
-                  else page_nval).astype(np.int64)
-        total = int(counts.sum())
-        n_pages = len(counts)
-        out_idx = np.zeros(n_pages, dtype=np.int64)
-        out_idx[1:] = np.cumsum(counts)[:-1]
-        pre = torch.empty(total + 1, dtype=torch.int32, device=dev)
-        sfx = torch.empty(total + 1, dtype=torch.int32, device=dev)
-        suf_pos = torch.empty(n_pages, dtype=torch.int64, device=dev)
-        status = self._status(n_pages)
-        counts_dev = self._up(counts.astype(np.int32))
-        out_idx_dev = self._up(out_idx)
-        ext.delta_byte_array_lengths_batch(
-            page_buf, self._up(val_start), self._up(val_end), counts_dev,
-            out_idx_dev, pre, sfx, suf_pos, status)
-        self._check(status, 'deltaba-len:' + ch['name'])
-        lens = (pre[:total] + sfx[:total]).to(torch.int64)
-        val_off = torch.cumsum(lens, 0) - lens
-        total_bytes = int((val_off[-1] + lens[-1]).item()) if total else 0
-        page_bytes = int((val_end - val_start).sum())
-        if total_bytes < 0 or total_bytes > max(1 << 20,
-                                                64 * page_bytes):
-            raise RuntimeError(
-                'DELTA_BYTE_ARRAY column {!r}: implausible materialized '
-                'size {} from {} page bytes (corrupt lengths?)'
-                .format(ch['name'], total_bytes, page_bytes))
-        out = torch.empty(total_bytes + _SLACK, dtype=torch.uint8,
-                          device=dev)
-        st2 = self._status(n_pages)
-        ext.delta_byte_array_reconstruct_batch(
-            page_buf, counts_dev, out_idx_dev, pre, sfx, suf_pos, val_off,
-            out, st2)
-        self._check(st2, 'deltaba-rec:' + ch['name'])
-        col = ByteArrayColumn(out, val_off, lens.to(torch.int32), None,
-                              None, total)
-        if valid is not None and nonnull_per_page is not None and \
-                not bool((nonnull_per_page == page_nval).all()):
-            col.valid = valid
-        return col
-
-    def _delta_fixed(self, ext, dev, page_buf, val_start, val_end,
-                     page_nval, phys, ch):
-        """DELTA_BINARY_PACKED int columns (wave-per-page shfl prefix
-        scan kernel); what pyarrow/Spark v2 writers emit for ints."""
-        dtype, esize = _PHYS_TO_TORCH[phys]
-        counts = page_nval.astype(np.int32)
-        total = int(counts.sum())
-        out_off = np.zeros(len(counts), dtype=np.int64)
-        out_off[1:] = np.cumsum(counts)[:-1]
-        out = torch.empty(total * esize + _SLACK, dtype=torch.uint8,
-                          device=dev)
-        status = self._status(len(counts))
-        ext.delta_binary_packed_batch(
-            page_buf, self._up(val_start), self._up(val_end),
-            self._up(counts), self._up(out_off), out, esize, status)
-        self._check(status, 'delta:' + ch['name'])
-        return out[:total * esize].view(dtype)
-
-    def _delta_length_byte_array(self, ext, dev, page_buf, val_start,
-                                 val_end, page_nval, nonnull_per_page,
-                                 valid, ch):
-        """DELTA_LENGTH_BYTE_ARRAY -> per-value (offset, length) tables
-        into the page buffer; flows into the standard ByteArrayColumn
-        consumers (strings/ndarray codecs)."""
-        counts = (nonnull_per_page if nonnull_per_page is not None
-                  else page_nval).astype(np.int64)
-        total = int(counts.sum())
-        out_idx = np.zeros(len(counts), dtype=np.int64)
-        out_idx[1:] = np.cumsum(counts)[:-1]
-        val_off = torch.empty(total, dtype=torch.int64, device=dev)
-        val_len = torch.empty(total, dtype=torch.int32, device=dev)
-        status = self._status(len(counts))
-        ext.delta_length_byte_array_batch(
-            page_buf, self._up(val_start), self._up(val_end),
-            self._up(counts.astype(np.int32)), self._up(out_idx), val_off,
-            val_len, status)
-        self._check(status, 'deltaba:' + ch['name'])
-        col = ByteArrayColumn(page_buf, val_off, val_len, None, None, total)
-        if valid is not None and nonnull_per_page is not None and \
-                not bool((nonnull_per_page == page_nval).all()):
-            col.valid = valid
-        return col
+    def _decode_levels(self, pg):
+        """Definition levels -> (per-row validity, non-null count per
+        page); the counts place the value sections and cost one host
+        sync."""
+        n = len(pg.page_nval)
+        levels = torch.empty(int(pg.page_nval.sum()), dtype=torch.int32,
+                             device=self.device)
+        status = self._status(n)
+        self._ext.rle_hybrid_decode_batch(
+            pg.lev_buf, self._up(pg.lev_start), self._up(pg.lev_end),
+            torch.full((n,), pg.lev_bits, dtype=torch.int32,
+                       device=self.device),
+            self._up(pg.page_nval.astype(np.int32)),
+            self._up(_excl_scan(pg.page_nval)), levels, status)
+        self._check(status, 'deflevels:' + pg.name)
+        valid = levels.bool() if pg.lev_present is None \
+            else levels == pg.lev_present
+        nonnull = np.array(
+            [int(v.sum().item()) for v in valid.split(pg.page_nval.tolist())],
+            dtype=np.int64)
+        return valid, nonnull
 
     # ------------------------------------------------------------------
     _FILL_PATTERNS = {
@@ -880,244 +731,251 @@ class GpuRowGroupDecoder(object):
                                                      .get(phys, 0))
         return self._FILL_PATTERNS.get(phys, 0)
 
-    def _plain_fixed_fused(self, ext, dev, page_buf, p_start, p_end,
-                           page_nval, row0, max_def, n_rows, phys, name,
-                           fill=None):
-        dtype, esize = _PHYS_TO_TORCH[phys]
-        total = int(page_nval.sum())
+    def _plain_fixed(self, pg, esize, fill, want_valid=False):
+        """The fused kernel: PLAIN values of ``esize`` bytes scattered to
+        their rows, null slots set to ``fill``, levels decoded in the same
+        launch per ``pg.def_mode``.  Returns (row bytes, per-row validity
+        bytes — empty unless ``want_valid`` and the column has levels)."""
+        dev = self.device
+        total = int(pg.page_nval.sum())
         out = torch.empty(total * esize + _SLACK, dtype=torch.uint8,
                           device=dev)
-        status = self._status(len(p_start))
+        status = self._status(len(pg.page_nval))
         empty8 = torch.empty(0, dtype=torch.uint8, device=dev)
         empty64 = torch.empty(0, dtype=torch.int64, device=dev)
-        ext.plain_fixed_decode_batch(
-            page_buf, self._up(p_start), self._up(p_end),
-            self._up(page_nval.astype(np.int32)), self._up(row0),
-            1 if max_def > 0 else 0, esize,
-            self._FILL_PATTERNS[phys] if fill is None else fill,
-            empty8, empty64, empty64,
-            out, empty8, status)
-        self._check(status, 'plainfixed:' + name)
-        return out[:total * esize].view(dtype)
+        valid_out = torch.empty(total, dtype=torch.uint8, device=dev) \
+            if want_valid and pg.def_mode else empty8
+        sep = pg.lev_buf is not None  # levels outside the value spans
+        self._ext.plain_fixed_decode_batch(
+            pg.val_buf, self._up(pg.val_start), self._up(pg.val_end),
+            self._up(pg.page_nval.astype(np.int32)),
+            self._up(_excl_scan(pg.page_nval)), pg.def_mode, esize, fill,
+            pg.lev_buf if sep else empty8,
+            self._up(pg.lev_start) if sep else empty64,
+            self._up(pg.lev_end - pg.lev_start) if sep else empty64,
+            out, valid_out, status)
+        self._check(status, 'plainfixed:' + pg.name)
+        return out[:total * esize], valid_out
 
-    def _decode_v2_chunk(self, ext, dev, dbuf, host_buf, ch, schema,
-                         pages, data_idx, n_rows):
-        """DataPageV2: levels are stored uncompressed with explicit byte
-        lengths; only the values section is compressed (Parquet format
-        spec).  Supported for PLAIN fixed-width columns; everything else
-        takes the CPU assist."""
-        phys = ch['physical']
-        enc = pages['encoding'].numpy()
-        supported_enc = {_ENC_PLAIN, _ENC_DELTA_BINARY,
-                         _ENC_DELTA_LENGTH_BA, _ENC_DELTA_BA,
-                         _ENC_BYTE_STREAM_SPLIT}
-        supported_phys = set(_PHYS_TO_TORCH) | {'BYTE_ARRAY', 'BOOLEAN',
-                                                'FIXED_LEN_BYTE_ARRAY'}
-        if phys not in supported_phys or \
-                any(enc[i] not in supported_enc for i in data_idx) or \
-                len({enc[i] for i in data_idx}) != 1:
-            return self._cpu_assist_marker(ch['name'])
-        data_off = pages['data_off'].numpy()
-        comp_size = pages['comp_size'].numpy()
-        uncomp_size = pages['uncomp_size'].numpy()
-        num_values = pages['num_values'].numpy()
-        dl = pages['dl_bytes'].numpy()
-        rl = pages['rl_bytes'].numpy()
-        if rl[data_idx].any():
-            return self._cpu_assist_marker(ch['name'])  # nested types
-        idx = np.asarray(data_idx)
-        page_nval = num_values[idx].astype(np.int64)
-        lev_start = (data_off[idx] + rl[idx]).astype(np.int64)
-        lev_len = dl[idx].astype(np.int64)
-        val_comp_start = (data_off[idx] + rl[idx] + dl[idx]).astype(np.int64)
-        # V2 compresses only the values section, and a page may individually
-        # opt out via is_compressed (writers skip compression when it does
-        # not shrink the page)
-        v2c = pages['v2_is_compressed'].numpy()[idx].astype(bool)
-        chunk_compressed = ch['compression'] in ('SNAPPY', 'GZIP', 'LZ4')
-        page_compressed = v2c & chunk_compressed
-        n = len(idx)
-        if page_compressed.any():
-            v_un = (uncomp_size[idx] - dl[idx] - rl[idx]).astype(np.int64)
-            v_comp_end = (data_off[idx] + comp_size[idx]).astype(np.int64)
-            u_off = np.zeros(n, dtype=np.int64)
-            u_off[1:] = np.cumsum(v_un)[:-1]
-            vbuf = torch.empty(int(v_un.sum()) + _SLACK, dtype=torch.uint8,
-                               device=dev)
-            ci = np.nonzero(page_compressed)[0]
-            status = self._status(len(ci))
-            if ch['compression'] == 'SNAPPY':
-                ext.snappy_decompress_batch(
-                    dbuf, self._up(val_comp_start[ci]),
-                    self._up(v_comp_end[ci]),
-                    vbuf, self._up(u_off[ci]), self._up(v_un[ci]), status)
-            elif ch['compression'] == 'LZ4':
-                # values sections may carry the Hadoop framing (see
-                # _lz4_spans); parse on host, decompress raw blocks
-                blocks = self._lz4_spans(
-                    host_buf.numpy(), val_comp_start[ci],
-                    (v_comp_end - val_comp_start)[ci], v_un[ci])
-                status = self._status(len(blocks['src']))
-                blk_dst = u_off[ci][blocks['page']] + blocks['dst_rel']
-                ext.lz4_decompress_batch(
-                    dbuf, self._up(blocks['src']),
-                    self._up(blocks['src'] + blocks['src_len']),
-                    vbuf, self._up(blk_dst), self._up(blocks['dst_len']),
-                    status)
-            else:
-                produced = torch.zeros(len(ci), dtype=torch.int64,
-                                       device=dev)
-                ext.inflate_batch(
-                    dbuf, self._up(val_comp_start[ci]),
-                    self._up((v_comp_end - val_comp_start)[ci]),
-                    torch.arange(len(ci), dtype=torch.int32, device=dev),
-                    torch.ones(len(ci), dtype=torch.int32, device=dev),
-                    vbuf, self._up(u_off[ci]), self._up(v_un[ci]), produced,
-                    2, status)
-            self._check(status, 'v2-decompress:' + ch['name'])
-            ri = np.nonzero(~page_compressed)[0]
-            if len(ri):
-                # raw pages inside a compressed chunk: copy bytes into their
-                # vbuf slots so the decode kernel sees one buffer
-                ext.varlen_gather(dbuf, self._up(val_comp_start[ri]),
-                                  self._up(v_un[ri]), vbuf,
-                                  self._up(u_off[ri]))
-            val_buf = vbuf
-            val_start = u_off
-            val_end = u_off + v_un
-        else:
-            val_buf = dbuf
-            val_start = val_comp_start
-            val_end = (data_off[idx] + comp_size[idx]).astype(np.int64)
-        row0 = np.zeros(n, dtype=np.int64)
-        row0[1:] = np.cumsum(page_nval)[:-1]
-        data_enc = enc[idx[0]]
-        if data_enc == _ENC_PLAIN and phys in _PHYS_TO_TORCH:
-            dtype, esize = _PHYS_TO_TORCH[phys]
-            total = int(page_nval.sum())
-            out = torch.empty(total * esize + _SLACK, dtype=torch.uint8,
-                              device=dev)
-            status2 = self._status(n)
-            has_def = 2 if ch['max_def'] > 0 else 0
-            empty8 = torch.empty(0, dtype=torch.uint8, device=dev)
-            ext.plain_fixed_decode_batch(
-                val_buf, self._up(val_start), self._up(val_end),
-                self._up(page_nval.astype(np.int32)), self._up(row0),
-                has_def, esize, self._fill_for(schema, ch['name'], phys),
-                dbuf, self._up(lev_start), self._up(lev_len),
-                out, empty8, status2)
-            self._check(status2, 'v2-plainfixed:' + ch['name'])
-            return out[:total * esize].view(dtype)
+    def _int96_timestamps(self, pg):
+        """PLAIN INT96 (legacy Spark timestamps): 8B nanos-in-day +
+        4B julian day -> int64 nanoseconds since the unix epoch; the
+        reader boundary surfaces datetime64[ns]."""
+        out, valid_out = self._plain_fixed(pg, 12, 0, want_valid=True)
+        total = out.numel() // 12
+        m = out.view(total, 12)
+        nanos = m[:, :8].contiguous().view(torch.int64).reshape(total)
+        day = m[:, 8:12].contiguous().view(torch.int32).reshape(total) \
+            .to(torch.int64)
+        ns = (day - 2440588) * 86_400_000_000_000 + nanos
+        if pg.def_mode:
+            # null rows -> int64 min == numpy NaT after the boundary's
+            # datetime64 view (CPU-route parity)
+            ns = torch.where(valid_out.bool(), ns,
+                             torch.tensor(np.iinfo(np.int64).min,
+                                          dtype=torch.int64,
+                                          device=self.device))
+        return ns
 
-        # other encodings share the V1 helpers; V2 levels (uncompressed,
-        # no length prefix) decode here to validity/non-null counts
-        valid = None
-        nonnull_per_page = None
-        if ch['max_def'] > 0:
-            md = int(ch['max_def'])
-            bw = max(1, int(np.ceil(np.log2(md + 1))))
-            lv_off = np.zeros(n + 1, dtype=np.int64)
-            lv_off[1:] = np.cumsum(page_nval)
-            levels = torch.empty(int(lv_off[-1]), dtype=torch.int32,
-                                 device=dev)
-            lst = self._status(n)
-            ext.rle_hybrid_decode_batch(
-                dbuf, self._up(lev_start), self._up(lev_start + lev_len),
-                torch.full((n,), bw, dtype=torch.int32, device=dev),
-                self._up(page_nval.astype(np.int32)),
-                self._up(lv_off[:-1]), levels, lst)
-            self._check(lst, 'v2-deflevels:' + ch['name'])
-            valid = levels == md
-            vmat = valid.split([int(x) for x in page_nval])
-            nonnull_per_page = np.array(
-                [int(v.sum().item()) for v in vmat], dtype=np.int64)
-        all_valid = nonnull_per_page is None or \
-            bool((nonnull_per_page == page_nval).all())
-        if data_enc == _ENC_PLAIN and phys == 'BYTE_ARRAY':
-            self._plan_entry = {}
-            return self._plain_byte_array(
-                ext, dev, val_buf, host_buf, val_start, val_end, page_nval,
-                nonnull_per_page, valid, False, ch)
-        if data_enc == _ENC_PLAIN and phys == 'BOOLEAN' and all_valid:
-            return self._bool_plain(ext, dev, val_buf, val_start,
-                                    page_nval)
-        if data_enc == _ENC_PLAIN and phys == 'FIXED_LEN_BYTE_ARRAY' and \
-                ch.get('type_length', 0) > 0:
-            return self._plain_flba(ext, dev, val_buf, host_buf, val_start,
-                                    page_nval, nonnull_per_page, valid,
-                                    False, schema, ch)
-        if data_enc == _ENC_DELTA_BINARY and phys in ('INT32', 'INT64') \
-                and all_valid:
-            return self._delta_fixed(ext, dev, val_buf, val_start, val_end,
-                                     page_nval, phys, ch)
-        if data_enc == _ENC_DELTA_LENGTH_BA and phys == 'BYTE_ARRAY':
-            return self._delta_length_byte_array(
-                ext, dev, val_buf, val_start, val_end, page_nval,
-                nonnull_per_page, valid, ch)
-        if data_enc == _ENC_DELTA_BA and phys == 'BYTE_ARRAY':
-            return self._delta_byte_array(
-                ext, dev, val_buf, val_start, val_end, page_nval,
-                nonnull_per_page, valid, ch)
-        if data_enc == _ENC_BYTE_STREAM_SPLIT and phys in _PHYS_TO_TORCH \
-                and all_valid:
-            return self._byte_stream_split(ext, dev, val_buf, val_start,
-                                           page_nval, phys)
-        return self._cpu_assist_marker(ch['name'])
-
-    def _plain_byte_array(self, ext, dev, page_buf, host_buf, val_start,
-                          val_end, page_nval, nonnull_per_page, valid,
-                          host_visible, ch):
-        counts = nonnull_per_page if nonnull_per_page is not None \
-            else page_nval
+    def _plain_byte_array(self, pg, counts, valid, all_valid, host_buf,
+                          plan):
+        """PLAIN BYTE_ARRAY -> per-value (offset, length) tables into the
+        page buffer.  ``plan`` is the chunk's prepare_host entry: for a
+        host-visible chunk it may already hold the offsets and the parsed
+        image headers."""
         total = int(counts.sum())
-        plan = getattr(self, '_plan_entry', {}) or {}
-        if host_visible and 'host_off' in plan:
+        planned = pg.host_visible and 'host_off' in plan
+        if planned:
             # offsets were already scanned on host by prepare_host (in the
             # IO thread) — upload them instead of launching the serial scan
             # kernel (which is latency-bound at a handful of pages)
             val_off = self._up(plan['host_off'])
             val_len = self._up(plan['host_len'].astype(np.int32))
         else:
-            o_off = np.zeros(len(counts), dtype=np.int64)
-            o_off[1:] = np.cumsum(counts)[:-1]
-            val_off = torch.empty(total, dtype=torch.int64, device=dev)
-            val_len = torch.empty(total, dtype=torch.int32, device=dev)
+            val_off = torch.empty(total, dtype=torch.int64,
+                                  device=self.device)
+            val_len = torch.empty(total, dtype=torch.int32,
+                                  device=self.device)
             status = self._status(len(counts))
-            ext.byte_array_offsets_batch(
-                page_buf, self._up(val_start), self._up(val_end),
+            self._ext.byte_array_offsets_batch(
+                pg.val_buf, self._up(pg.val_start), self._up(pg.val_end),
                 self._up(counts.astype(np.int32)),
-                self._up(o_off), val_off, val_len, status)
-            self._check(status, 'bytearray:' + ch['name'])
-        host_off = None
-        host_len = None
-        if host_visible:
-            if 'host_off' in plan:
-                host_off = plan['host_off']
-                host_len = plan.get('host_len')
-            else:
-                # mirror the scan on host (native C++) so codecs needing
-                # header parsing (jpeg/png) can see the bytes
-                ho = ext.byte_array_host_offsets(
-                    host_buf, torch.from_numpy(val_start),
-                    torch.from_numpy(counts.astype(np.int64)))
-                host_off = ho['off'].numpy()
-                host_len = ho['len'].numpy()
-        col = ByteArrayColumn(page_buf, val_off, val_len,
-                              host_buf if host_visible else None,
+                self._up(_excl_scan(counts)), val_off, val_len, status)
+            self._check(status, 'bytearray:' + pg.name)
+        host_off = host_len = None
+        if planned:
+            host_off, host_len = plan['host_off'], plan.get('host_len')
+        elif pg.host_visible:
+            # mirror the scan on host (native C++) so codecs needing
+            # header parsing (jpeg/png) can see the bytes
+            ho = self._ext.byte_array_host_offsets(
+                host_buf, torch.from_numpy(pg.val_start),
+                torch.from_numpy(counts))
+            host_off, host_len = ho['off'].numpy(), ho['len'].numpy()
+        col = ByteArrayColumn(pg.val_buf, val_off, val_len,
+                              host_buf if pg.host_visible else None,
                               host_off, total)
         col.host_val_len = host_len
-        # per-ROW validity; normalized to None when every row is non-null
-        if valid is not None and nonnull_per_page is not None and \
-                not bool((nonnull_per_page == page_nval).all()):
-            col.valid = valid
+        if pg.host_visible:
+            col.jpeg_meta = plan.get('jpeg_meta')
+            col.png_meta = plan.get('png_meta')
+        return _tag_valid(col, valid, all_valid)
 
-        col.jpeg_meta = plan.get('jpeg_meta')
-        col.png_meta = plan.get('png_meta')
-        return col
+    def _plain_flba(self, pg, counts, valid, all_valid, host_buf, schema,
+                    ch):
+        """PLAIN FIXED_LEN_BYTE_ARRAY: values are contiguous with a
+        fixed stride.  float16 (logical Float16) views the gathered bytes
+        directly as a half tensor; everything else becomes a fixed-stride
+        ByteArrayColumn (bytes at the boundary)."""
+        L = int(ch['type_length'])
+        total = int(counts.sum())
+        field = schema.fields.get(ch['name'])
+        if field is not None and field.numpy_dtype is np.float16 and \
+                all_valid and L == 2:
+            out = torch.empty(total * L + _SLACK, dtype=torch.uint8,
+                              device=self.device)
+            self._ext.varlen_gather(pg.val_buf, self._up(pg.val_start),
+                                    self._up(counts * L), out,
+                                    self._up(_excl_scan(counts * L)))
+            return out[:total * L].view(torch.float16)
+        starts = np.concatenate(
+            [vs + np.arange(c, dtype=np.int64) * L
+             for vs, c in zip(pg.val_start, counts)]) if total else \
+            np.zeros(0, dtype=np.int64)
+        col = ByteArrayColumn(pg.val_buf, self._up(starts),
+                              torch.full((total,), L, dtype=torch.int32,
+                                         device=self.device),
+                              host_buf if pg.host_visible else None,
+                              starts if pg.host_visible else None, total)
+        if pg.host_visible:
+            col.host_val_len = np.full(total, L, dtype=np.int64)
+        return _tag_valid(col, valid, all_valid)
 
-    def _dict_byte_array(self, ext, dev, page_buf, page_start, dict_idx,
-                         num_values, size_arr, val_start, val_end, page_nval,
-                         nonnull_per_page, valid, ch):
+    def _bool_plain(self, pg):
+        """PLAIN BOOLEAN: bit-packed LSB-first -> bool tensor."""
+        counts = pg.page_nval.astype(np.int32)
+        total = int(counts.sum())
+        out = torch.empty(total + _SLACK, dtype=torch.uint8,
+                          device=self.device)
+        self._ext.bool_unpack_batch(pg.val_buf, self._up(pg.val_start),
+                                    self._up(counts),
+                                    self._up(_excl_scan(counts)), out)
+        return out[:total].to(torch.bool)
+
+    def _bool_rle(self, pg):
+        """RLE BOOLEAN: u32 length prefix + hybrid runs (bit width 1)."""
+        counts = pg.page_nval.astype(np.int32)
+        out = torch.empty(int(counts.sum()), dtype=torch.int32,
+                          device=self.device)
+        status = self._status(len(counts))
+        self._ext.rle_hybrid_decode_batch(
+            pg.val_buf, self._up(pg.val_start + 4), self._up(pg.val_end),
+            torch.ones(len(counts), dtype=torch.int32, device=self.device),
+            self._up(counts), self._up(_excl_scan(counts)), out, status)
+        self._check(status, 'rlebool:' + pg.name)
+        return out.to(torch.bool)
+
+    def _byte_stream_split(self, pg, phys):
+        """BYTE_STREAM_SPLIT: de-interleave K byte planes."""
+        dtype, esize = _PHYS_TO_TORCH[phys]
+        counts = pg.page_nval.astype(np.int32)
+        total = int(counts.sum())
+        out = torch.empty(total * esize + _SLACK, dtype=torch.uint8,
+                          device=self.device)
+        self._ext.byte_stream_split_batch(
+            pg.val_buf, self._up(pg.val_start), self._up(counts),
+            self._up(_excl_scan(counts)), out, esize)
+        return out[:total * esize].view(dtype)
+
+    def _delta_byte_array(self, pg, counts, valid, all_valid):
+        """DELTA_BYTE_ARRAY (front-coded strings): lengths pass -> exact
+        output sizing (ONE host sync — unavoidable: materialized size is
+        data-dependent) -> reconstruct pass.  Values land in a fresh
+        device buffer; standard ByteArrayColumn consumers follow."""
+        ext, dev = self._ext, self.device
+        total = int(counts.sum())
+        n_pages = len(counts)
+        pre = torch.empty(total + 1, dtype=torch.int32, device=dev)
+        sfx = torch.empty(total + 1, dtype=torch.int32, device=dev)
+        suf_pos = torch.empty(n_pages, dtype=torch.int64, device=dev)
+        status = self._status(n_pages)
+        counts_dev = self._up(counts.astype(np.int32))
+        out_idx_dev = self._up(_excl_scan(counts))
+        ext.delta_byte_array_lengths_batch(
+            pg.val_buf, self._up(pg.val_start), self._up(pg.val_end),
+            counts_dev, out_idx_dev, pre, sfx, suf_pos, status)
+        self._check(status, 'deltaba-len:' + pg.name)
+        lens = (pre[:total] + sfx[:total]).to(torch.int64)
+        val_off = torch.cumsum(lens, 0) - lens
+        total_bytes = int((val_off[-1] + lens[-1]).item()) if total else 0
+        page_bytes = int((pg.val_end - pg.val_start).sum())
+        if total_bytes < 0 or total_bytes > max(1 << 20,
+                                                64 * page_bytes):
+            raise RuntimeError(
+                'DELTA_BYTE_ARRAY column {!r}: implausible materialized '
+                'size {} from {} page bytes (corrupt lengths?)'
+                .format(pg.name, total_bytes, page_bytes))
+        out = torch.empty(total_bytes + _SLACK, dtype=torch.uint8,
+                          device=dev)
+        st2 = self._status(n_pages)
+        ext.delta_byte_array_reconstruct_batch(
+            pg.val_buf, counts_dev, out_idx_dev, pre, sfx, suf_pos, val_off,
+            out, st2)
+        self._check(st2, 'deltaba-rec:' + pg.name)
+        col = ByteArrayColumn(out, val_off, lens.to(torch.int32), None,
+                              None, total)
+        return _tag_valid(col, valid, all_valid)
+
+    def _delta_fixed(self, pg, phys):
+        """DELTA_BINARY_PACKED int columns (wave-per-page shfl prefix
+        scan kernel); what pyarrow/Spark v2 writers emit for ints."""
+        dtype, esize = _PHYS_TO_TORCH[phys]
+        counts = pg.page_nval.astype(np.int32)
+        total = int(counts.sum())
+        out = torch.empty(total * esize + _SLACK, dtype=torch.uint8,
+                          device=self.device)
+        status = self._status(len(counts))
+        self._ext.delta_binary_packed_batch(
+            pg.val_buf, self._up(pg.val_start), self._up(pg.val_end),
+            self._up(counts), self._up(_excl_scan(counts)), out, esize,
+            status)
+        self._check(status, 'delta:' + pg.name)
+        return out[:total * esize].view(dtype)
+
+    def _delta_length_byte_array(self, pg, counts, valid, all_valid):
+        """DELTA_LENGTH_BYTE_ARRAY -> per-value (offset, length) tables
+        into the page buffer; flows into the standard ByteArrayColumn
+        consumers (strings/ndarray codecs)."""
+        total = int(counts.sum())
+        val_off = torch.empty(total, dtype=torch.int64, device=self.device)
+        val_len = torch.empty(total, dtype=torch.int32, device=self.device)
+        status = self._status(len(counts))
+        self._ext.delta_length_byte_array_batch(
+            pg.val_buf, self._up(pg.val_start), self._up(pg.val_end),
+            self._up(counts.astype(np.int32)), self._up(_excl_scan(counts)),
+            val_off, val_len, status)
+        self._check(status, 'deltaba:' + pg.name)
+        col = ByteArrayColumn(pg.val_buf, val_off, val_len, None, None,
+                              total)
+        return _tag_valid(col, valid, all_valid)
+
+    def _dict_indices(self, pg, counts):
+        """Dictionary indices of a chunk's data pages: first byte of each
+        value section = bit width (a tiny D2H), then hybrid runs — one
+        index per NON-NULL row."""
+        bw = torch.stack([pg.val_buf[int(s)] for s in pg.val_start]).cpu() \
+            .numpy().astype(np.int32)
+        indices = torch.empty(int(counts.sum()), dtype=torch.int32,
+                              device=self.device)
+        status = self._status(len(counts))
+        self._ext.rle_hybrid_decode_batch(
+            pg.val_buf, self._up(pg.val_start + 1), self._up(pg.val_end),
+            self._up(bw), self._up(counts.astype(np.int32)),
+            self._up(_excl_scan(counts)), indices, status)
+        self._check(status, 'dictidx:' + pg.name)
+        return indices.long()
+
+    def _dict_byte_array(self, pg, counts, valid, all_valid):
         """Dictionary-encoded binary column: decode the dictionary page's
         value offsets once, decode the RLE indices, and gather per-row
         (offset, length) — blob bytes are never copied.
@@ -1126,79 +984,36 @@ class GpuRowGroupDecoder(object):
         (indices only exist on device), so image codecs needing host header
         parsing fall back to CPU; the ndarray codecs decode fully on-GPU.
         """
-        di = dict_idx[0]
-        dict_n = int(num_values[di])
-        dstart = int(page_start[di])
-        dend = dstart + int(size_arr[di])
-        d_off = torch.empty(dict_n, dtype=torch.int64, device=dev)
-        d_len = torch.empty(dict_n, dtype=torch.int32, device=dev)
+        dstart, dend, dict_n = pg.dict_span
+        d_off = torch.empty(dict_n, dtype=torch.int64, device=self.device)
+        d_len = torch.empty(dict_n, dtype=torch.int32, device=self.device)
         status = self._status(1)
-        ext.byte_array_offsets_batch(
-            page_buf, self._up(np.array([dstart], dtype=np.int64)),
+        self._ext.byte_array_offsets_batch(
+            pg.val_buf, self._up(np.array([dstart], dtype=np.int64)),
             self._up(np.array([dend], dtype=np.int64)),
             self._up(np.array([dict_n], dtype=np.int32)),
             self._up(np.array([0], dtype=np.int64)), d_off, d_len, status)
-        self._check(status, 'dictba-dict:' + ch['name'])
-
-        # RLE indices exist only for NON-NULL rows (def levels already
-        # decoded by the caller when the column is OPTIONAL)
-        counts = nonnull_per_page if nonnull_per_page is not None \
-            else page_nval
-        bw_t = torch.stack([page_buf[int(s)] for s in val_start]).cpu()
-        bw = bw_t.numpy().astype(np.int32)
-        i_off = np.zeros(len(counts) + 1, dtype=np.int64)
-        i_off[1:] = np.cumsum(counts)
-        indices = torch.empty(int(i_off[-1]), dtype=torch.int32, device=dev)
-        st2 = self._status(len(counts))
-        ext.rle_hybrid_decode_batch(
-            page_buf, self._up(val_start + 1), self._up(val_end),
-            self._up(bw), self._up(counts.astype(np.int32)),
-            self._up(i_off[:-1]), indices, st2)
-        self._check(st2, 'dictba-idx:' + ch['name'])
-        idx = indices.long()
-        col = ByteArrayColumn(page_buf, d_off.index_select(0, idx),
+        self._check(status, 'dictba-dict:' + pg.name)
+        idx = self._dict_indices(pg, counts)
+        col = ByteArrayColumn(pg.val_buf, d_off.index_select(0, idx),
                               d_len.index_select(0, idx), None, None,
-                              int(i_off[-1]))
-        if valid is not None and nonnull_per_page is not None and \
-                not bool((nonnull_per_page == page_nval).all()):
-            col.valid = valid
-        return col
+                              int(counts.sum()))
+        return _tag_valid(col, valid, all_valid)
 
-    def _dict_fixed(self, ext, dev, page_buf, page_start, dict_idx,
-                    num_values, size_arr, val_start, val_end, page_nval,
-                    nonnull_per_page, valid, n_rows, phys):
+    def _dict_fixed(self, pg, counts, valid, n_rows, phys):
+        """Dictionary-encoded fixed-width column: gather the dictionary
+        page's values, index them, scatter to the valid rows."""
+        dev = self.device
         dtype, esize = _PHYS_TO_TORCH[phys]
-        di = dict_idx[0]
-        dict_n = int(num_values[di])
-        dstart = int(page_start[di])
+        dstart, _, dict_n = pg.dict_span
         flat = torch.empty(dict_n * esize + _SLACK, dtype=torch.uint8,
                            device=dev)
-        ext.varlen_gather(page_buf,
-                          torch.tensor([dstart], dtype=torch.int64,
-                                       device=dev),
-                          torch.tensor([dict_n * esize], dtype=torch.int64,
-                                       device=dev),
-                          flat,
-                          torch.tensor([0], dtype=torch.int64, device=dev))
-        dict_vals = flat[:dict_n * esize].view(dtype)
-
-        counts = nonnull_per_page if nonnull_per_page is not None \
-            else page_nval
-        # data page: first byte = bit width, then hybrid runs
-        bw = np.empty(len(val_start), dtype=np.int32)
-        # read bit-width bytes (tiny D2H)
-        bw_t = torch.stack([page_buf[int(s)] for s in val_start]).cpu()
-        bw[:] = bw_t.numpy()
-        i_off = np.zeros(len(counts) + 1, dtype=np.int64)
-        i_off[1:] = np.cumsum(counts)
-        indices = torch.empty(int(i_off[-1]), dtype=torch.int32, device=dev)
-        status = self._status(len(counts))
-        ext.rle_hybrid_decode_batch(
-            page_buf, self._up(val_start + 1), self._up(val_end),
-            self._up(bw), self._up(counts.astype(np.int32)),
-            self._up(i_off[:-1]), indices, status)
-        self._check(status, 'dictidx:' + phys)
-        values = dict_vals[indices.long()]
+        self._ext.varlen_gather(
+            pg.val_buf, torch.tensor([dstart], dtype=torch.int64, device=dev),
+            torch.tensor([dict_n * esize], dtype=torch.int64, device=dev),
+            flat, torch.tensor([0], dtype=torch.int64, device=dev))
+        values = flat[:dict_n * esize].view(dtype)[
+            self._dict_indices(pg, counts)]
         if valid is None:
             return values
         out = torch.zeros(n_rows, dtype=dtype, device=dev)
@@ -1303,37 +1118,39 @@ class GpuRowGroupDecoder(object):
     # ------------------------------------------------------------------
     def decode_ndarray_column(self, col, field):
         """NdarrayCodec: npy containers -> dense [n, *shape] tensor."""
-        ext = self._ext
-        dev = self.device
-        np_dtype = np.dtype(field.numpy_dtype)
         shape = tuple(field.shape)
         if any(d is None for d in shape):
             return None  # variable shape -> CPU assist
+        return self._npy_rows(col.device_buf, col.val_off, col.val_len,
+                              col.n, field, shape)
+
+    def _npy_rows(self, buf, val_off, val_len, n, field, shape):
+        """n npy containers at ``buf[val_off:val_off + val_len]`` -> dense
+        [n, *shape] tensor of the field's dtype: locate the payloads, gather
+        them row by row."""
+        ext = self._ext
+        dev = self.device
+        np_dtype = np.dtype(field.numpy_dtype)
         elem = int(np.prod(shape)) if shape else 1
         row_bytes = elem * np_dtype.itemsize
-        pay_off = torch.empty(col.n, dtype=torch.int64, device=dev)
-        pay_len = torch.empty(col.n, dtype=torch.int64, device=dev)
+        pay_off = torch.empty(n, dtype=torch.int64, device=dev)
+        pay_len = torch.empty(n, dtype=torch.int64, device=dev)
         status = self._status(1)
-        ext.npy_payload_offsets(col.device_buf, col.val_off, col.val_len,
-                                pay_off, pay_len, status)
+        ext.npy_payload_offsets(buf, val_off, val_len, pay_off, pay_len,
+                                status)
         self._check(status, 'npy:' + field.name)
-        out = torch.empty(col.n * row_bytes + _SLACK, dtype=torch.uint8,
+        out = torch.empty(n * row_bytes + _SLACK, dtype=torch.uint8,
                           device=dev)
-        dst_off = torch.arange(col.n, dtype=torch.int64, device=dev) \
-            * row_bytes
-        ext.varlen_gather(col.device_buf, pay_off, pay_len, out, dst_off)
+        dst_off = torch.arange(n, dtype=torch.int64, device=dev) * row_bytes
+        ext.varlen_gather(buf, pay_off, pay_len, out, dst_off)
         # reinterpret raw bytes at the SAME width, then widen unsigned types
         # torch can't represent (mirrors _sanitize_pytorch_types, reference
         # pytorch.py:40-70)
         view_dtype = _np_view_torch(np_dtype)
         if view_dtype is None:
             return None
-        t = out[:col.n * row_bytes].view(view_dtype).view((col.n,) + shape)
-        if np_dtype == np.dtype(np.uint16):
-            t = t.to(torch.int32) & 0xFFFF
-        elif np_dtype == np.dtype(np.uint32):
-            t = t.to(torch.int64) & 0xFFFFFFFF
-        return t
+        t = out[:n * row_bytes].view(view_dtype).view((n,) + shape)
+        return _widen_unsigned(t, np_dtype)
 
     def _is_npz_column(self, col, field):
         """True when the column's payloads are np.savez(_compressed) zip
@@ -1418,21 +1235,8 @@ class GpuRowGroupDecoder(object):
                           seg_count, raw, raw_off, raw_cap, produced, mode,
                           status)
         self._check(status, 'inflate:' + field.name)
-        pay_off = torch.empty(n, dtype=torch.int64, device=dev)
-        pay_len = torch.empty(n, dtype=torch.int64, device=dev)
-        st2 = self._status(1)
-        ext.npy_payload_offsets(raw, raw_off, produced.to(torch.int32),
-                                pay_off, pay_len, st2)
-        self._check(st2, 'npy:' + field.name)
-        out = torch.empty(n * row_bytes + _SLACK, dtype=torch.uint8,
-                          device=dev)
-        dst_off = torch.arange(n, dtype=torch.int64, device=dev) * row_bytes
-        ext.varlen_gather(raw, pay_off, pay_len, out, dst_off)
-        view_dtype = _np_view_torch(np_dtype)
-        if view_dtype is None:
-            return None
-        t = out[:n * row_bytes].view(view_dtype).view((n,) + shape)
-        return _widen_unsigned(t, np_dtype)
+        return self._npy_rows(raw, raw_off, produced.to(torch.int32), n,
+                              field, shape)
 
     def decode_string_column(self, col, field):
         """String / raw-binary column: values stay device-resident through
@@ -1512,8 +1316,7 @@ class GpuRowGroupDecoder(object):
         depth = meta['bit_depth'].numpy()
         row_bytes = meta['row_bytes'].numpy().astype(np.int64)
         raw_size = meta['raw_size'].numpy()
-        raw_off = np.zeros(n, dtype=np.int64)
-        raw_off[1:] = np.cumsum(raw_size)[:-1]
+        raw_off = _excl_scan(raw_size)
         raw = torch.empty(int(raw_size.sum()) + _SLACK, dtype=torch.uint8,
                           device=dev)
         produced = torch.zeros(n, dtype=torch.int64, device=dev)
@@ -1527,8 +1330,7 @@ class GpuRowGroupDecoder(object):
                           status)
         self._check(status, 'png-inflate:' + field.name)
         out_bytes = row_bytes * heights
-        out_off = np.zeros(n, dtype=np.int64)
-        out_off[1:] = np.cumsum(out_bytes)[:-1]
+        out_off = _excl_scan(out_bytes)
         out = torch.empty(int(out_bytes.sum()) + _SLACK, dtype=torch.uint8,
                           device=dev)
         st2 = self._status(n)
@@ -1601,8 +1403,7 @@ class GpuRowGroupDecoder(object):
                 self.device.type == 'cuda':
             H, W = int(heights[0]), int(widths[0])
             out_px = (widths.astype(np.int64) * heights * 3)
-            out_off = np.zeros(n, dtype=np.int64)
-            out_off[1:] = np.cumsum(out_px)[:-1]
+            out_off = _excl_scan(out_px)
             out = torch.empty(n, 3, H, W, dtype=torch.float32, device=dev)
             cache = getattr(self, '_fused_norm_cache', None)
             if cache is None:
@@ -1624,8 +1425,7 @@ class GpuRowGroupDecoder(object):
             return out
         out_bytes = (widths.astype(np.int64) * heights *
                      np.where(ncomp == 3, 3, 1))
-        out_off = np.zeros(n, dtype=np.int64)
-        out_off[1:] = np.cumsum(out_bytes)[:-1]
+        out_off = _excl_scan(out_bytes)
         out = torch.empty(int(out_bytes.sum()), dtype=torch.uint8,
                           device=dev)
         status = self._status(max(n_segs, 1))

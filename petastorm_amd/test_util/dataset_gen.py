@@ -252,6 +252,42 @@ def create_rich_scalar_dataset(url, num_rows=200, rowgroup_size=50):
     return rows
 
 
+def create_nullable_pages_dataset(url, data_page_version, compression,
+                                  num_rows=600, seed=5):
+    """One row group of several small data pages per column, without
+    dictionaries: ``id`` int64 PLAIN (no nulls), and under one seeded 20 %
+    null mask ``s`` string PLAIN, ``s2`` string DELTA_LENGTH_BYTE_ARRAY and
+    ``fb`` binary(4) PLAIN.  Returns the written pyarrow table."""
+    import pyarrow as pa
+    import pyarrow.parquet as pq
+    from petastorm_amd.fs_utils import get_filesystem_and_path_or_paths
+    null = np.random.RandomState(seed).rand(num_rows) < 0.2
+
+    def col(make, typ):
+        return pa.array([None if null[i] else make(i)
+                         for i in range(num_rows)], typ)
+
+    table = pa.table({
+        'id': pa.array(np.arange(num_rows, dtype=np.int64)),
+        's': col(lambda i: 'row-%d-%s' % (i, 'x' * (i % 23)), pa.string()),
+        's2': col(lambda i: 'é%d' % i * (i % 5), pa.string()),
+        # compressible, or a V2 writer stores the page uncompressed
+        'fb': col(lambda i: bytes([48 + i % 7]) * 4, pa.binary(4)),
+    })
+    fs, path = get_filesystem_and_path_or_paths(url)
+    fs.makedirs(path, exist_ok=True)
+    # write_batch_size: pyarrow tests the page size once per batch, so the
+    # default 1024 would put all rows on one page
+    pq.write_table(table, path + '/data.parquet', row_group_size=num_rows,
+                   compression=compression, use_dictionary=False,
+                   data_page_version=data_page_version,
+                   data_page_size=2 << 10, write_batch_size=50,
+                   column_encoding={'id': 'PLAIN', 's': 'PLAIN',
+                                    's2': 'DELTA_LENGTH_BYTE_ARRAY',
+                                    'fb': 'PLAIN'})
+    return table
+
+
 def create_many_columns_dataset(url, num_rows=25, num_columns=1000):
     """1000-int32-column plain store (reference tests/test_common.py:
     248-294)."""

@@ -44,7 +44,12 @@ class _StubExt(object):
     _OUTPUTS = {'rle_hybrid_decode_batch': (6,),
                 'plain_fixed_decode_batch': (11,),
                 'varlen_gather': (3,),
-                'delta_byte_array_lengths_batch': (5, 6, 7)}
+                'delta_byte_array_lengths_batch': (5, 6, 7),
+                # decompressed pages: the V1 level-length prefix of a
+                # nullable column is read back from this buffer
+                'snappy_decompress_batch': (3,),
+                'lz4_decompress_batch': (3,),
+                'inflate_batch': (5,)}
 
     def __getattr__(self, name):
         if name in self._KERNELS:
@@ -56,6 +61,38 @@ class _StubExt(object):
                         args[i].zero_()
             return stub
         return getattr(self._real, name)
+
+
+def _seq(spec):
+    return [{'snappy': 'snappy_decompress_batch',
+             'lz4': 'lz4_decompress_batch',
+             'fixed': 'plain_fixed_decode_batch',
+             'ba_offsets': 'byte_array_offsets_batch',
+             'rle': 'rle_hybrid_decode_batch',
+             'npy': 'npy_payload_offsets'}.get(k, k) for k in spec.split()]
+
+
+# exact ordered kernel launches per dry-run store
+_SEQ = {
+    'scalar_none': _seq('fixed fixed fixed'),
+    'scalar_snappy': _seq('snappy fixed snappy fixed snappy fixed'),
+    'scalar_gzip': _seq('inflate_batch fixed inflate_batch fixed '
+                        'inflate_batch fixed'),
+    'lz4_scalar': _seq('lz4 fixed lz4 fixed'),
+    'imagenet': _seq('snappy fixed jpeg_decode_batch'),
+    'sequence': _seq('snappy fixed snappy ba_offsets npy varlen_gather'),
+    'png': _seq('snappy fixed inflate_batch png_unfilter_batch'),
+    'compressed_ndarray': _seq('snappy fixed inflate_batch npy '
+                               'varlen_gather'),
+    'npz': _seq('snappy fixed snappy ba_offsets inflate_batch npy '
+                'varlen_gather'),
+    'dictionary': _seq('rle varlen_gather rle'),
+    'delta': _seq('delta_binary_packed_batch '
+                  'delta_length_byte_array_batch'),
+    'bool_bss_delta_ba': _seq('byte_stream_split_batch bool_unpack_batch '
+                              'delta_byte_array_lengths_batch '
+                              'delta_byte_array_reconstruct_batch'),
+}
 
 
 @pytest.fixture()
@@ -92,6 +129,7 @@ def test_dryrun_scalar_paths(stub_decoder, tmp_path, compression):
     assert 'plain_fixed_decode_batch' in stub.calls
     if compression == 'snappy':
         assert 'snappy_decompress_batch' in stub.calls
+    assert stub.calls == _SEQ['scalar_' + compression]
 
 
 def test_dryrun_imagenet_paths(stub_decoder, tmp_path):
@@ -106,6 +144,7 @@ def test_dryrun_imagenet_paths(stub_decoder, tmp_path):
     decoded = dec.decode_jpeg_column(col, schema.fields['image'])
     assert decoded is not None and decoded.shape == (8, 224, 224, 3)
     assert 'jpeg_decode_batch' in stub.calls
+    assert stub.calls == _SEQ['imagenet']
 
 
 def test_dryrun_sequence_and_png_paths(stub_decoder, tmp_path):
@@ -119,6 +158,7 @@ def test_dryrun_sequence_and_png_paths(stub_decoder, tmp_path):
                                         schema.fields['tokens'])
     assert decoded.shape == (30, 1024)
     assert 'npy_payload_offsets' in stub.calls
+    assert stub.calls == _SEQ['sequence']
 
     url2 = 'file://' + str(tmp_path / 'hw')
     create_hello_world_dataset(url2, num_rows=4, rowgroup_size_mb=4)
@@ -127,6 +167,7 @@ def test_dryrun_sequence_and_png_paths(stub_decoder, tmp_path):
     assert png is not None and png.shape == (4, 128, 256, 3)
     assert 'inflate_batch' in stub.calls
     assert 'png_unfilter_batch' in stub.calls
+    assert stub.calls == _SEQ['sequence'] + _SEQ['png']
 
 
 def test_dryrun_compressed_ndarray(stub_decoder, tmp_path):
@@ -148,6 +189,7 @@ def test_dryrun_compressed_ndarray(stub_decoder, tmp_path):
     z = dec.decode_compressed_ndarray_column(out['mat'], sch.fields['mat'])
     assert z.shape == (20, 8, 4)
     assert 'inflate_batch' in stub.calls
+    assert stub.calls == _SEQ['compressed_ndarray']
 
 
 def test_dryrun_lz4_scalar(stub_decoder, tmp_path):
@@ -159,6 +201,7 @@ def test_dryrun_lz4_scalar(stub_decoder, tmp_path):
                           compression='lz4')
     out = _decode_all(dec, url, ['id', 'f0'])
     assert 'lz4_decompress_batch' in stub.calls
+    assert stub.calls == _SEQ['lz4_scalar']
     assert not dec.cpu_assist_columns
 
 
@@ -320,6 +363,7 @@ def test_dryrun_dictionary_paths(stub_decoder, tmp_path):
     dec.flush_status()
     assert 'rle_hybrid_decode_batch' in stub.calls
     assert not dec.cpu_assist_columns
+    assert stub.calls == _SEQ['dictionary']
 
 
 def test_dryrun_npz_interop_column(stub_decoder, tmp_path):
@@ -339,6 +383,7 @@ def test_dryrun_npz_interop_column(stub_decoder, tmp_path):
                                              sch.fields['matrix_z'])
     assert z is None or z.shape == (4, 4, 5)
     assert 'inflate_batch' in stub.calls or 'varlen_gather' in stub.calls
+    assert stub.calls == _SEQ['npz']
 
 
 def test_dryrun_string_column_host_visible_exact(stub_decoder, tmp_path):
@@ -403,6 +448,7 @@ def test_dryrun_delta_encodings(stub_decoder, tmp_path):
     assert out['s'] is not None and out['s'].n == 200
     assert 'delta_binary_packed_batch' in stub.calls
     assert 'delta_length_byte_array_batch' in stub.calls
+    assert stub.calls == _SEQ['delta']
     assert not dec.cpu_assist_columns
 
 
@@ -434,6 +480,7 @@ def test_dryrun_bool_bss_delta_ba(stub_decoder, tmp_path):
     assert 'byte_stream_split_batch' in stub.calls
     assert 'bool_unpack_batch' in stub.calls
     assert 'delta_byte_array_lengths_batch' in stub.calls
+    assert stub.calls == _SEQ['bool_bss_delta_ba']
     assert not dec.cpu_assist_columns
 
 
@@ -458,6 +505,37 @@ def test_dryrun_flba(stub_decoder, tmp_path):
     got = dec.decode_string_column(out['fb'], sch.fields['fb'])
     assert got.tolist() == [b'ab12'] * n
     assert not dec.cpu_assist_columns
+
+
+@pytest.mark.parametrize('compression', ['none', 'snappy', 'gzip', 'lz4',
+                                         'zstd'])
+@pytest.mark.parametrize('version', ['1.0', '2.0'])
+def test_dryrun_nullable_pages_v1_v2(stub_decoder, tmp_path, version,
+                                     compression):
+    """Nullable PLAIN / DELTA_LENGTH_BYTE_ARRAY strings and nullable FLBA
+    over several pages take the GPU route under every codec.  The expected
+    launches do not depend on the page version: V1 and V2 give one and the
+    same sequence."""
+    from petastorm_amd.test_util.dataset_gen import \
+        create_nullable_pages_dataset
+    dec, stub = stub_decoder
+    url = 'file://' + str(tmp_path / 'np')
+    create_nullable_pages_dataset(url, version, compression)
+    out, _ = _decode_all(dec, url, ['id', 's', 's2', 'fb'])
+    assert not dec.cpu_assist_columns
+    assert out['id'].shape == (600,)
+    for name in ('s', 's2', 'fb'):
+        assert isinstance(out[name], ByteArrayColumn)
+        # the stubbed level decode yields all-zero levels: every row null
+        assert out[name].n == 0 and out[name].valid.shape == (600,)
+    # zstd decompresses on the host; the others once per column chunk
+    decompress = {'snappy': 'snappy ', 'gzip': 'inflate_batch ',
+                  'lz4': 'lz4 '}.get(compression, '')
+    assert stub.calls == _seq(''.join(decompress + column for column in (
+        'fixed ',                                  # id
+        'rle ba_offsets ',                         # s
+        'rle delta_length_byte_array_batch ',      # s2
+        'rle ')))                                  # fb: offsets on the host
 
 
 def test_cuda_route_requires_gpu_at_construction(tmp_path):

@@ -1577,6 +1577,30 @@ def test_v2_pages_delta_and_bool_gpu(ext, tmp_path):
     assert np.concatenate(got['s']).tolist() == strs
 
 
+@pytest.mark.parametrize('compression', ['none', 'snappy', 'gzip', 'lz4'])
+def test_v2_nullable_strings_and_flba_gpu(ext, tmp_path, compression):
+    """DataPageV2 nullable columns off the fused kernel (PLAIN and
+    DELTA_LENGTH_BYTE_ARRAY strings, FIXED_LEN_BYTE_ARRAY), several pages:
+    values and null positions exact against pyarrow, no CPU assist."""
+    from petastorm_amd import make_batch_reader
+    from petastorm_amd.test_util.dataset_gen import \
+        create_nullable_pages_dataset
+    url = 'file://' + str(tmp_path / ('v2null_' + compression))
+    want = create_nullable_pages_dataset(url, '2.0', compression).to_pydict()
+    got = {k: [] for k in want}
+    with make_batch_reader(url, device='cuda',
+                           shuffle_row_groups=False) as r:
+        for batch in r:
+            for k in got:
+                v = getattr(batch, k)
+                got[k].extend(v.cpu().numpy().tolist() if hasattr(v, 'cpu')
+                              else np.asarray(v, dtype=object).tolist())
+        assert r.diagnostics['cpu_assist_columns'] == []
+    assert any(v is None for v in want['s'])
+    for k in want:
+        assert got[k] == want[k], k
+
+
 def test_unsigned_logical_types_gpu(ext, tmp_path):
     """Unsigned logical types over signed physical storage: values exact
     at full range (uint8/16/32/64), widened per the framework convention
