@@ -30,7 +30,8 @@ import torch
 
 from petastorm_amd.errors import NoDataAvailableError
 from petastorm_amd.etl import dataset_metadata as dsm
-from petastorm_amd.gpu.decoder import ByteArrayColumn, GpuRowGroupDecoder
+from petastorm_amd.gpu.decoder import (ByteArrayColumn, GpuRowGroupDecoder,
+                                       ListColumn)
 from petastorm_amd.gpu.hbm_cache import HbmCache
 from petastorm_amd.ngram import NGram
 from petastorm_amd.parallel import epochs as epoch_sync
@@ -567,6 +568,13 @@ class GpuBatchReader(object):
                     columns[name] = decoded
             else:
                 dt = field.numpy_dtype if field is not None else None
+                if isinstance(col, ListColumn):
+                    # dense [n, k] tensor (widened below like a scalar
+                    # column), per-row arrays, or the assist
+                    col = self._decoder.decode_list_column(col, field)
+                    if col is None:
+                        assist.append(name)
+                        continue
                 if isinstance(col, torch.Tensor):
                     if dt is np.datetime64:
                         # DATE/TIMESTAMP: physical ints decoded on device;

@@ -116,6 +116,19 @@ void byte_stream_split_batch(torch::Tensor page_buf, torch::Tensor start,
 void bool_unpack_batch(torch::Tensor page_buf, torch::Tensor start,
                        torch::Tensor n_values, torch::Tensor out_off,
                        torch::Tensor out);
+void list_count_batch(torch::Tensor rep, torch::Tensor def,
+                      torch::Tensor n_entries, torch::Tensor entry0,
+                      int64_t def_slot, int64_t max_def,
+                      torch::Tensor counts);
+void list_assemble_batch(torch::Tensor rep, torch::Tensor def,
+                         torch::Tensor n_entries, torch::Tensor entry0,
+                         torch::Tensor bases, torch::Tensor val_buf,
+                         torch::Tensor val_start, torch::Tensor val_end,
+                         int64_t esize, int64_t fill_pattern,
+                         int64_t def_slot, int64_t max_def,
+                         bool list_nullable, torch::Tensor values,
+                         torch::Tensor offsets, torch::Tensor list_valid,
+                         torch::Tensor elem_valid, torch::Tensor status);
 void jpeg_decode_fused_batch(torch::Tensor data, py::dict meta,
                              torch::Tensor coef, torch::Tensor samples,
                              torch::Tensor out, torch::Tensor out_off,
@@ -179,6 +192,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "BYTE_STREAM_SPLIT de-interleave");
   m.def("bool_unpack_batch", &psa::bool_unpack_batch,
         "PLAIN boolean bit-unpack");
+  m.def("list_count_batch", &psa::list_count_batch,
+        "List column levels -> per-page (rows, slots, values) counts");
+  m.def("list_assemble_batch", &psa::list_assemble_batch,
+        "List column levels + PLAIN values -> offsets, validity, elements");
   m.def("jpeg_decode_fused_batch", &psa::jpeg_decode_fused_batch,
         "JPEG decode with fused YCbCr->RGB + normalize + NCHW fp32 "
         "epilogue (skips the NHWC uint8 intermediate)");

@@ -924,4 +924,189 @@ void bool_unpack_batch(torch::Tensor page_buf, torch::Tensor start,
                      n);
 }
 
+// ---------------------------------------------------------------------------
+// List columns (max_rep == 1): repetition + definition levels -> row offsets,
+// with the PLAIN values scattered into element slots.
+//
+// Input is the chunk's decoded levels, rep[L] and def[L] (one
+// rle_hybrid_decode_batch launch), page j owning entries
+// [entry0[j], entry0[j] + n_entries[j]).  Per entry:
+//   rep == 0          starts a row (a list, a null list or an empty list)
+//   def >= def_slot   occupies an element slot
+//   def == max_def    the slot holds a stored value (else a null element)
+// Two wave-per-page kernels: list_count_batch counts the three per page; a
+// device-side exclusive cumsum of the counts gives every page its row, slot
+// and value base; list_assemble_batch then writes offsets / validity and
+// copies the values.  A row may continue across a page boundary (V1 allows
+// it), which is why row and slot indices come from the bases and not from
+// the page start.
+// ---------------------------------------------------------------------------
+
+// lanes-below-me mask; lane 63 special-cased ((1ull << 64) is UB)
+__device__ __forceinline__ unsigned long long lanes_below(int lane) {
+  return (lane < 63) ? ((1ull << lane) - 1ull) : 0x7FFFFFFFFFFFFFFFull;
+}
+
+__global__ void list_count_kernel(
+    const int32_t* __restrict__ rep, const int32_t* __restrict__ def,
+    const int32_t* __restrict__ n_entries, const int64_t* __restrict__ entry0,
+    int32_t def_slot, int32_t max_def,
+    int64_t* __restrict__ counts,  // [n_pages, 3]: rows, slots, values
+    int n_pages) {
+  const int waves_per_block = blockDim.x / PSA_WAVE;
+  const int page = blockIdx.x * waves_per_block + (threadIdx.x / PSA_WAVE);
+  if (page >= n_pages) return;
+  const int lane = lane_id();
+  const int32_t want = n_entries[page];
+  const int32_t* r = rep + entry0[page];
+  const int32_t* d = def + entry0[page];
+  int64_t rows = 0, slots = 0, vals = 0;
+  for (int32_t base = 0; base < want; base += PSA_WAVE) {
+    const int32_t i = base + lane;
+    const bool in = i < want;
+    const int32_t rv = in ? r[i] : 1, dv = in ? d[i] : -1;
+    rows += __popcll(__ballot(in && rv == 0));
+    slots += __popcll(__ballot(in && dv >= def_slot));
+    vals += __popcll(__ballot(in && dv == max_def));
+  }
+  if (lane == 0) {
+    counts[page * 3 + 0] = rows;
+    counts[page * 3 + 1] = slots;
+    counts[page * 3 + 2] = vals;
+  }
+}
+
+void list_count_batch(torch::Tensor rep, torch::Tensor def,
+                      torch::Tensor n_entries, torch::Tensor entry0,
+                      int64_t def_slot, int64_t max_def,
+                      torch::Tensor counts) {
+  int n = (int)n_entries.numel();
+  if (!n) return;
+  TORCH_CHECK(counts.numel() == (int64_t)n * 3, "counts must be [n_pages, 3]");
+  const int WPB = 4;
+  hipStream_t stream = c10::hip::getCurrentHIPStream();
+  hipLaunchKernelGGL(list_count_kernel, dim3((n + WPB - 1) / WPB),
+                     dim3(WPB * PSA_WAVE), 0, stream,
+                     rep.data_ptr<int32_t>(), def.data_ptr<int32_t>(),
+                     n_entries.data_ptr<int32_t>(),
+                     entry0.data_ptr<int64_t>(), (int32_t)def_slot,
+                     (int32_t)max_def, counts.data_ptr<int64_t>(), n);
+}
+
+// status codes: 1 = the chunk's first entry continues a row (rep != 0);
+// 2 = a row index >= n_rows or a slot index >= slot_cap; 3 = the page's
+// value span is too short for its stored values.  Every index is checked
+// BEFORE the access it guards; a failed check skips the access.
+__global__ void list_assemble_kernel(
+    const int32_t* __restrict__ rep, const int32_t* __restrict__ def,
+    const int32_t* __restrict__ n_entries, const int64_t* __restrict__ entry0,
+    const int64_t* __restrict__ bases,  // [n_pages, 3] exclusive scan of counts
+    const uint8_t* __restrict__ val_buf, const int64_t* __restrict__ val_start,
+    const int64_t* __restrict__ val_end, int32_t esize, uint64_t fill_pattern,
+    int32_t def_slot, int32_t max_def, int32_t list_nullable, int64_t n_rows,
+    int64_t slot_cap, uint8_t* __restrict__ values,
+    int64_t* __restrict__ offsets,       // [n_rows + 1]
+    uint8_t* __restrict__ list_valid,    // [n_rows]
+    uint8_t* __restrict__ elem_valid,    // [slot_cap]
+    int32_t* __restrict__ status, int n_pages) {
+  const int waves_per_block = blockDim.x / PSA_WAVE;
+  const int page = blockIdx.x * waves_per_block + (threadIdx.x / PSA_WAVE);
+  if (page >= n_pages) return;
+  const int lane = lane_id();
+  const int32_t want = n_entries[page];
+  const int32_t* r = rep + entry0[page];
+  const int32_t* d = def + entry0[page];
+  const int64_t vlo = val_start[page], vhi = val_end[page];
+  // running cursors across the 64-entry steps
+  int64_t row_cursor = bases[page * 3 + 0];
+  int64_t slot_cursor = bases[page * 3 + 1];
+  int64_t val_cursor = 0;  // values are addressed inside the page's own span
+  for (int32_t base = 0; base < want; base += PSA_WAVE) {
+    const int32_t i = base + lane;
+    const bool in = i < want;
+    const int32_t rv = in ? r[i] : 1, dv = in ? d[i] : -1;
+    const bool is_row = in && rv == 0;
+    const bool is_slot = in && dv >= def_slot;
+    const bool has_val = in && dv == max_def;
+    const unsigned long long row_mask = __ballot(is_row);
+    const unsigned long long slot_mask = __ballot(is_slot);
+    const unsigned long long val_mask = __ballot(has_val);
+    const unsigned long long below = lanes_below(lane);
+    // slots before this entry: also the offset of a row starting here
+    const int64_t slot = slot_cursor + __popcll(slot_mask & below);
+    if (page == 0 && i == 0 && in && rv != 0) status[page] = 1;
+    if (is_row) {
+      const int64_t row = row_cursor + __popcll(row_mask & below);
+      if (row < n_rows) {
+        offsets[row] = slot;
+        list_valid[row] = (uint8_t)((list_nullable && dv == 0) ? 0 : 1);
+      } else {
+        status[page] = 2;
+      }
+    }
+    if (is_slot) {
+      if (slot >= slot_cap) {
+        status[page] = 2;
+      } else if (has_val) {
+        const int64_t src =
+            vlo + (val_cursor + __popcll(val_mask & below)) * esize;
+        if (src >= vlo && src + esize <= vhi) {
+          copy_elem(values + slot * esize, val_buf + src, esize);
+          elem_valid[slot] = 1;
+        } else {
+          status[page] = 3;
+        }
+      } else {
+        fill_elem(values + slot * esize, fill_pattern, esize);
+        elem_valid[slot] = 0;
+      }
+    }
+    row_cursor += __popcll(row_mask);
+    slot_cursor += __popcll(slot_mask);
+    val_cursor += __popcll(val_mask);
+  }
+  if (page == n_pages - 1 && lane == 0) offsets[n_rows] = slot_cursor;
+}
+
+void list_assemble_batch(torch::Tensor rep, torch::Tensor def,
+                         torch::Tensor n_entries, torch::Tensor entry0,
+                         torch::Tensor bases, torch::Tensor val_buf,
+                         torch::Tensor val_start, torch::Tensor val_end,
+                         int64_t esize, int64_t fill_pattern,
+                         int64_t def_slot, int64_t max_def,
+                         bool list_nullable, torch::Tensor values,
+                         torch::Tensor offsets, torch::Tensor list_valid,
+                         torch::Tensor elem_valid, torch::Tensor status) {
+  int n = (int)n_entries.numel();
+  if (!n) return;
+  TORCH_CHECK(esize == 4 || esize == 8, "list elements are 4 or 8 bytes");
+  TORCH_CHECK(bases.numel() == (int64_t)n * 3, "bases must be [n_pages, 3]");
+  TORCH_CHECK(offsets.numel() >= 1, "offsets must hold n_rows + 1 entries");
+  const int64_t n_rows = offsets.numel() - 1;
+  const int64_t slot_cap = elem_valid.numel();
+  TORCH_CHECK(list_valid.numel() >= n_rows, "list_valid shorter than n_rows");
+  TORCH_CHECK(values.numel() >= slot_cap * esize,
+              "values shorter than elem_valid * esize");
+  TORCH_CHECK(status.numel() >= n && val_start.numel() >= n &&
+              val_end.numel() >= n && entry0.numel() >= n,
+              "per-page arrays shorter than n_pages");
+  const int WPB = 4;
+  hipStream_t stream = c10::hip::getCurrentHIPStream();
+  hipLaunchKernelGGL(list_assemble_kernel, dim3((n + WPB - 1) / WPB),
+                     dim3(WPB * PSA_WAVE), 0, stream,
+                     rep.data_ptr<int32_t>(), def.data_ptr<int32_t>(),
+                     n_entries.data_ptr<int32_t>(),
+                     entry0.data_ptr<int64_t>(), bases.data_ptr<int64_t>(),
+                     val_buf.data_ptr<uint8_t>(),
+                     val_start.data_ptr<int64_t>(),
+                     val_end.data_ptr<int64_t>(), (int32_t)esize,
+                     (uint64_t)fill_pattern, (int32_t)def_slot,
+                     (int32_t)max_def, (int32_t)(list_nullable ? 1 : 0),
+                     n_rows, slot_cap, values.data_ptr<uint8_t>(),
+                     offsets.data_ptr<int64_t>(),
+                     list_valid.data_ptr<uint8_t>(),
+                     elem_valid.data_ptr<uint8_t>(),
+                     status.data_ptr<int32_t>(), n);
+}
+
 }  // namespace psa

@@ -288,6 +288,50 @@ def create_nullable_pages_dataset(url, data_page_version, compression,
     return table
 
 
+def create_list_dataset(url, data_page_version, compression, num_rows=300,
+                        rowgroup_size=None):
+    """List columns over several small PLAIN data pages, without
+    dictionaries, so rows straddle pages and 64-entry steps: ``id`` int64;
+    ``rag`` list<float32> of 0-8 elements with empty (``i % 11 == 3``) and
+    null (``i % 17 == 5``) lists; ``fix`` fixed_size_list<int32>[9]; ``req``
+    list<int64 not null> of uniform length 9; ``ragnull`` like ``rag`` with
+    a null element wherever ``(i + j) % 7 == 2``.  Returns the written
+    pyarrow table."""
+    import pyarrow as pa
+    import pyarrow.parquet as pq
+    from petastorm_amd.fs_utils import get_filesystem_and_path_or_paths
+
+    def rag(i, with_null_elems):
+        if i % 17 == 5:
+            return None
+        if i % 11 == 3:
+            return []
+        return [None if with_null_elems and (i + j) % 7 == 2
+                else float(i) + j / 8.0 for j in range(i % 9)]
+
+    table = pa.table({
+        'id': pa.array(np.arange(num_rows, dtype=np.int64)),
+        'rag': pa.array([rag(i, False) for i in range(num_rows)],
+                        pa.list_(pa.float32())),
+        'fix': pa.array([list(range(i, i + 9)) for i in range(num_rows)],
+                        pa.list_(pa.int32(), 9)),
+        'req': pa.array(
+            [[(i << 33) - j for j in range(9)] for i in range(num_rows)],
+            pa.list_(pa.field('element', pa.int64(), nullable=False))),
+        'ragnull': pa.array([rag(i, True) for i in range(num_rows)],
+                            pa.list_(pa.float32())),
+    })
+    fs, path = get_filesystem_and_path_or_paths(url)
+    fs.makedirs(path, exist_ok=True)
+    # write_batch_size: see create_nullable_pages_dataset
+    pq.write_table(table, path + '/data.parquet',
+                   row_group_size=rowgroup_size or num_rows,
+                   compression=compression, use_dictionary=False,
+                   data_page_version=data_page_version,
+                   data_page_size=512, write_batch_size=20)
+    return table
+
+
 def create_many_columns_dataset(url, num_rows=25, num_columns=1000):
     """1000-int32-column plain store (reference tests/test_common.py:
     248-294)."""
